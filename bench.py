@@ -1,18 +1,25 @@
 #!/usr/bin/env python3
 """DMVAE training-step benchmark on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): images/sec (train), MNIST-shaped K=10 z_dim=64
 batch=4096 per GPU, bf16 MFMA GEMMs, synthetic 28x28 inputs resident in HBM.
 One "step" = batch assembly + forward + loss + backward + (gradient all-reduce)
 + Adam, i.e. one session.run([loss, train_step]) of code/base_models.py:126-129.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+A plain run sets up, warms up (W steps, then the untimed settle regions, whose
+steps are undone), times exactly K steps in one region and prints ONE JSON line
+(rank 0) with the driver's contract.  --dump-outputs DIR writes what the last
+timed step computed (loss terms, trained parameters) as DIR/<name>.npy.
+--full adds what the headline figure does not need:
+  --repeats (3) timed regions, the line reporting the median one
+  "exchange"     : N > 1, the exposed part of the gradient exchange (eager steps)
   "roofline"     : the dominant kernel family; durations are each dispatch's own
                    begin -> end timestamps (event pair bound to the dispatch by
                    hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports) over a
                    few eager steps of the same process and shapes
+  "elbo50"       : cfg2 at N = 1, 50 epochs bf16 against the fp32 parity engine
   "cpu_baseline" : the oracle (CPU restatement of the reference step, float32,
                    NumPy/OpenBLAS on the box's host cores) on a bounded sample.
 """
@@ -29,6 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "deep-mixture-vae_amd"))
 
 PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA, MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0       # HBM3E spec
+DUMP_BYTES = 64 << 20       # --dump-outputs writes at most this much
 
 
 # BASELINE.json configs as presets (per-GPU sizes; cfg4 / cfg5 name a global batch of 65 536 over 8 GPUs = 8192 per GPU).
@@ -49,8 +57,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=3, help="the timed region (exactly --steps steps between barriers) is run this many "
-                    "times back to back; the line reports the MEDIAN region (SURVEY 8d), all regions in repeat_ms_per_step")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: --repeats regions, the "
+                    "exchange diagnostics (N > 1), the per-kernel roofline, the ELBO leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default="", metavar="DIR", help="after the timed steps, write what the last "
+                    "one computed -- loss terms and trained parameters -- as DIR/<name>.npy (float32; a fixed, seeded sample of every "
+                    "parameter when they exceed 64 MB in all)")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region (exactly --steps steps between barriers) is run this many "
+                    "times back to back; the line reports the MEDIAN region (SURVEY 8d), all regions in repeat_ms_per_step "
+                    "(default 1; 3 with --full)")
     ap.add_argument("--config", default="", choices=[""] + sorted(PRESETS), help="a BASELINE.json config as a preset of the shape flags "
                     "below (per-GPU batch; cfg4 = the north star's scaling point, 8192 per GPU, D=256, K=50); default = cfg2, the metric")
     ap.add_argument("--batch", type=int, default=4096, help="per-GPU batch (cfg2: 4096)")
@@ -72,22 +86,28 @@ def parse():
                     "(priors.py:170-181) feeding the cluster_sample branch of the KL (priors.py:118-128), Gumbel noise from the device Philox stream")
     ap.add_argument("--temperature", type=float, default=1.0, help="tau of --mode relaxed")
     ap.add_argument("--stable-warmup", dest="stable_warmup", type=int, default=8, help="after --warmup steps, run untimed 20-step regions until two "
-                    "consecutive ones agree within 1 %% (the clock ramp: the first region after 5-20 steps reads 3-4 %% slow), at most this many; 0 = off")
+                    "consecutive ones agree within 1 %% (the clock ramp: the first region after 5-20 steps reads 3-4 %% slow), at most this many, "
+                    "then restore the training state they advanced; 0 = off")
     ap.add_argument("--rows", type=int, default=65536, help="synthetic dataset rows resident in HBM")
     ap.add_argument("--no-graph", action="store_true", help="issue the step eagerly instead of replaying a HIP graph")
     ap.add_argument("--deterministic", action="store_true", help="no float atomics (split-K off)")
-    ap.add_argument("--profile-steps", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--profile-steps", type=int, default=None, help="eager steps of the per-kernel roofline leg (default 0; 5 with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=20, help="timed oracle steps at the bench batch (after 3 warm-up steps)")
     ap.add_argument("--cpu-seconds", type=float, default=45.0, help="upper bound on the oracle's timed loop (larger configs stop early; the sample says so)")
-    ap.add_argument("--elbo-epochs", type=int, default=50, help="N = 1, the metric's config only: the metric's second half, ELBO@50ep -- this many "
-                    "epochs of bf16 training against the fp32 parity engine on identical batches and noise (0 = skip)")
+    ap.add_argument("--elbo-epochs", type=int, default=None, help="N = 1, the metric's config only: the metric's second half, ELBO@50ep -- this many "
+                    "epochs of bf16 training against the fp32 parity engine on identical batches and noise (default 0 = skip; 50 with --full)")
     ap.add_argument("--dp-dry-run", default="", choices=["", "overlap", "single", "sharded"],
                     help="N = 1 only: issue the data-parallel launch sequence (staged backward + stand-alone Adam, or whole "
                          "backward + Adam) with a no-op exchange, to price the N > 1 path's compute")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N > 1 (nccl = RCCL; gloo only to rehearse the multi-rank path on one GPU)")
     args = ap.parse_args()
+    for k, plain, full in (("repeats", 1, 3), ("profile_steps", 0, 5), ("elbo_epochs", 0, 50)):
+        if getattr(args, k) is None:
+            setattr(args, k, full if args.full else plain)
+    if not args.full:
+        args.no_cpu_baseline = True
     if args.config:
         for k, v in PRESETS[args.config].items():
             setattr(args, k, v)
@@ -200,6 +220,32 @@ def elbo_leg(args, data, epochs, StepEngine):
             "unit": "nats/image", "data": "synthetic 28x28 stand-in, %d rows, batch %d (no MNIST files in the image)" % (rows, B),
             "reference": "unpinned: TensorFlow is not installed, the reference publishes no ELBO value (BASELINE.md)",
             "wall_seconds": {k: round(v, 2) for k, v in secs.items()}}
+
+
+def training_state(eng):
+    """the device arrays a step advances: weights (and their bf16 shadow), Adam moments, step state (batch cursor, Adam t, noise step)"""
+    return [t for t in (eng.param, eng.param_bf16, eng.m, eng.v, eng.state_t) if t is not None]
+
+
+def dump_outputs(eng, st, out_dir):
+    """What the timed path hands its caller after its last step: that step's loss terms and the trained parameters (the fp32
+    master under bf16), float32, one DIR/<name>.npy each.  Were the parameters to exceed DUMP_BYTES in all, every one is cut to
+    the same share of its elements at positions drawn from a fixed seed, flattened: the same positions on every run and build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss_terms": np.array([st.last_loss, st.last_recon, st.last_klz, st.last_klc], dtype=np.float32)}
+    params = eng.get_parameters()
+    total = sum(4 * v.size for v in params.values())
+    keep = min(1.0, (DUMP_BYTES - 4096) / total)
+    for k, v in params.items():
+        v = v.astype(np.float32)
+        if keep < 1.0:
+            n = max(1, int(v.size * keep))
+            v = v.ravel()[np.sort(np.random.default_rng(0).choice(v.size, n, replace=False))]
+        arrays[k] = v
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": sum(v.nbytes for v in arrays.values()), "sampled": keep < 1.0}
 
 
 def respawn_ranks(args):
@@ -315,9 +361,12 @@ def main():
         step()
     # untimed: the chip's clock (and, N > 1, RCCL's channels) settle over the first few hundred microseconds of back-to-back steps --
     # region 1 of the round-3 driver line read 3.9 % slow behind 5 warm-up steps.  Run 20-step regions until two in a row agree
-    # within 1 % (every rank takes the same decision: the slowest rank's clock decides), then time.
+    # within 1 % (every rank takes the same decision: the slowest rank's clock decides), then time.  How many settle steps run
+    # depends on the clock, so the training state they advanced is put back: what the timed steps compute depends on
+    # --warmup and --steps alone (--dump-outputs).
     settle = []
     if args.stable_warmup > 0:
+        saved = [t.clone() for t in training_state(eng)]
         prev = None
         for _ in range(args.stable_warmup):
             torch.cuda.synchronize()
@@ -335,6 +384,10 @@ def main():
             if prev is not None and abs(cur - prev) <= 0.01 * prev:
                 break
             prev = cur
+        for t, s in zip(training_state(eng), saved):
+            t.copy_(s)
+        eng.write_state()           # (re-reads the restored step state; the next replay gathers the batch of the restored cursor)
+        del saved
     regions, rank_regions = [], []
     for _ in range(max(1, args.repeats)):       # each region: EXACTLY --steps steps between barrier + synchronize
         torch.cuda.synchronize()
@@ -361,12 +414,18 @@ def main():
         regions.append(el)
     elapsed = sorted(regions)[len(regions) // 2]               # the median region
     st = eng.read_state()
+    dumped = None
+    if args.dump_outputs:
+        if sync is not None and getattr(sync, "enabled", False):
+            eng.sync_master(ex)         # (a collective: sharded steps leave a rank's fp32 master current on its own slice only)
+        if rank == 0:
+            dumped = dump_outputs(eng, st, args.dump_outputs)
 
     # N > 1 (or a forced one-rank communicator): what of the exchange is EXPOSED -- the time from the end of the backward pass's last
     # kernel to the end of the step's last kernel or collective (event pair on the compute stream around everything
     # _step_with_exchange issues behind the backward pass), averaged over a few eager steps; and the step with a no-op exchange.
     exch = None
-    if sync is not None and getattr(sync, "enabled", False):
+    if args.full and sync is not None and getattr(sync, "enabled", False):
         exch = eng.measure_exchange(data, perm, sync, ex.grad_scale, steps=10)
         if world > 1:
             import torch.distributed as dist
@@ -447,7 +506,10 @@ def main():
         # tail, all-reduce MIN == MAX: parallel.ShardedExchange.self_check); a failed check raises on every rank before this line
         exch["self_check"] = getattr(eng, "_exchange_check", None) or ("not run (%s)" % ("all-reduce form: every rank applies the same sum" if not getattr(sync, "sharded", False) else "one rank"))
         out["exchange"] = exch
-    out["timing"] = "median of %d regions of %d steps, each bracketed by barrier + synchronize" % (len(regions), args.steps)
+    out["timing"] = ("median of %d regions of %d steps, each bracketed by barrier + synchronize" % (len(regions), args.steps) if len(regions) > 1
+                     else "one region of %d steps, bracketed by barrier + synchronize" % args.steps)
+    if dumped is not None:
+        out["outputs"] = dumped
     if rows:
         ps = float(args.profile_steps)
         # Per-kernel durations: each dispatch's OWN begin -> end timestamps (the event pair hipExtLaunchKernelGGL binds to

@@ -124,7 +124,8 @@ def test_plan_layout_under_address_sanitizer():
     spec.loader.exec_module(mod)
     so, rt = mod.build_host_asan()
     assert os.path.exists(so) and rt, (so, rt)
-    env = dict(os.environ, LD_PRELOAD=rt, DMVAE_HIP_LIB=so, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:exitcode=86",
+    preload = ":".join(p for p in (rt, os.environ.get("LD_PRELOAD", "")) if p)      # the ASan runtime first, whatever the environment preloads after it
+    env = dict(os.environ, LD_PRELOAD=preload, DMVAE_HIP_LIB=so, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:exitcode=86",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", PYTHONPATH=os.path.join(ROOT, "deep-mixture-vae_amd"))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "asan_plan_probe.py")], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "asan probe ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])

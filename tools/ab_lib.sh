@@ -4,12 +4,13 @@
 # alternates  DMVAE_HIP_LIB=build/variants/<variant>.so  and the in-tree library, 3 rounds, prints ms/step of every run.
 VAR=${1:?variant name}; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-mkdir -p "$ROOT/gpurun_out"
+OUT=${OUT:-$ROOT/bench_out}          # where the bench lines are written
+mkdir -p "$OUT"
 for r in 1 2 3; do
   for w in variant tree; do
     if [ $w = variant ]; then export DMVAE_HIP_LIB="$ROOT/deep-mixture-vae_amd/build/variants/$VAR.so"; else unset DMVAE_HIP_LIB; fi
-    python3 "$ROOT/bench.py" "$@" --no-cpu-baseline --elbo-epochs 0 > "$ROOT/gpurun_out/ab_${w}_$r.json" || exit 1
-    python3 - "$ROOT/gpurun_out/ab_${w}_$r.json" $w <<'PY'
+    python3 "$ROOT/bench.py" --full "$@" --no-cpu-baseline --elbo-epochs 0 > "$OUT/ab_${w}_$r.json" || exit 1
+    python3 - "$OUT/ab_${w}_$r.json" $w <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 ks = {k["kernel"]: k["ms_per_step"] for k in d.get("kernels", [])}

@@ -3,7 +3,7 @@
 # per-GPU shards) + cfg2 in fp32 parity mode -> gpurun_out/configs.jsonl
 cd $GRAFT_REPO_ROOT
 out=gpurun_out/configs.jsonl; : > $out
-run() { python3 bench.py "$@" --no-cpu-baseline --elbo-epochs 0 --profile-steps 3 2>/dev/null >> $out; }
+run() { python3 bench.py --full "$@" --no-cpu-baseline --elbo-epochs 0 --profile-steps 3 2>/dev/null >> $out; }
 run --config cfg1 --steps 200 --warmup 20
 run --config cfg2 --steps 200 --warmup 20
 run --config cfg2 --steps 50 --warmup 5 --dtype fp32

@@ -8,7 +8,7 @@ TAG=${1:-r01}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/profiles_$TAG
 mkdir -p $OUT
-ARGS="--cnn --enc_layers 500 --steps 30 --warmup 5"
+ARGS="--full --cnn --enc_layers 500 --steps 30 --warmup 5"
 python3 bench.py $ARGS > $OUT/${TAG}_cnn_bench.json 2> $OUT/${TAG}_cnn_bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_cnn_$TAG -o $TAG -- python3 bench.py $ARGS --no-cpu-baseline --profile-steps 0 > $OUT/${TAG}_cnn_bench_under_rocprof.json 2> /dev/null
 cp $(ls gpurun_out/prof_cnn_$TAG/*/*kernel_stats.csv gpurun_out/prof_cnn_$TAG/*kernel_stats.csv 2>/dev/null | head -1) $OUT/${TAG}_cnn_kernel_stats.csv

@@ -11,13 +11,13 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/profiles_$TAG
 mkdir -p $OUT profiles
 if [ -z "$CFG" ]; then
-    NAME=$TAG; ARGS="--steps 200 --warmup 20"
+    NAME=$TAG; ARGS="--full --steps 200 --warmup 20"
     TAG=$TAG tools/pmc_traffic.sh > $OUT/${TAG}_pmc_traffic_head.txt 2>&1
     cp gpurun_out/traffic.json profiles/traffic.json
     cp gpurun_out/traffic.json $OUT/traffic.json
     cp gpurun_out/pmc_traffic.txt $OUT/${TAG}_pmc_traffic.txt
 else
-    NAME=${TAG}_$CFG; ARGS="--config $CFG --steps 20 --warmup 3 --no-cpu-baseline"
+    NAME=${TAG}_$CFG; ARGS="--full --config $CFG --steps 20 --warmup 3 --no-cpu-baseline"
 fi
 python3 bench.py $ARGS > $OUT/${NAME}_bench.json 2> $OUT/${NAME}_bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$NAME -o $NAME -- python3 bench.py $ARGS --no-cpu-baseline --elbo-epochs 0 > $OUT/${NAME}_bench_under_rocprof.json 2> /dev/null

@@ -12,7 +12,7 @@ mkdir -p $O
 case "$1" in
 a)  tools/profile_round.sh $T > $O/log_a.txt 2>&1
     tools/pmc_sq.sh $T >> $O/log_a.txt 2>&1; cp gpurun_out/${T}_pmc_sq.txt $O/
-    python3 bench.py --mode relaxed --steps 200 --warmup 20 --no-cpu-baseline --elbo-epochs 0 > $O/${T}_relaxed_bench.json 2> $O/${T}_relaxed_bench.err
+    python3 bench.py --full --mode relaxed --steps 200 --warmup 20 --no-cpu-baseline --elbo-epochs 0 > $O/${T}_relaxed_bench.json 2> $O/${T}_relaxed_bench.err
     rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${T}_relaxed -o ${T}_relaxed -- python3 bench.py --mode relaxed --steps 200 --warmup 20 --no-cpu-baseline --elbo-epochs 0 > /dev/null 2>&1
     cp $(ls gpurun_out/prof_${T}_relaxed/*/*kernel_stats.csv gpurun_out/prof_${T}_relaxed/*kernel_stats.csv 2>/dev/null | head -1) $O/${T}_relaxed_kernel_stats.csv ;;
 c)  for c in cfg3 cfg4; do
