@@ -173,7 +173,8 @@ class DeepMixtureVAE(VAE):
                                   head_dim=self.head_dim, dec_layers=self.dec_layers, input_type=self.input_type,
                                   dtype=self.dtype, max_batch=self.batch_size, mode="relaxed" if self.gumbel else "exact",
                                   temperature=self.temperature, seed=self.seed + 7919 * sess.rank,
-                                  deterministic=self.deterministic, session=sess, cnn=self.cnn)
+                                  deterministic=self.deterministic, session=sess, cnn=self.cnn,
+                                  moe=getattr(self, "_moe_spec", None))     # (set by models.MoE: the experts' head on this gate)
         self._engine.init_parameters(self.seed)
         # names of the graph's placeholders / tensors (fetch through the methods below)
         self.X, self.epsilon, self.cluster = "X", "epsilon_Z", "epsilon_C"

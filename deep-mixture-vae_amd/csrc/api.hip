@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "moe_head.h"
 #include "measure.h"
 
 namespace dmvae {
@@ -220,6 +221,17 @@ struct dmvae_plan {
     int64_t o_cs_dl = -1, o_cs_dhzc = -1;
     std::vector<int64_t> o_cs_ddec, o_cs_denc;
     std::map<const void*, std::pair<const float*, int64_t>> csum_of;     // dY base pointer -> (partials, ld), filled during a pass
+    // mixture-of-experts attachment (dmvae_plan_attach_moe, models.py:10-163 of the reference): W_moe is the last weight matrix,
+    // b_moe the last bias of the tail; the workspace grows by the buffers below.  Plans without it keep their layout.
+    struct {
+        bool on = false;
+        dmvae_moe_config cfg{};
+        int EO = 0, EOp = 0;
+        PLayer L;                         // in = input_dim (featLearn off) or latent_dim (featLearn on), out = E * O
+        int64_t o_P = 0, o_dP = 0, o_inp = 0, o_dq = 0, o_pred = 0, o_part = 0, o_acc = 0;
+        int nblk = 0;
+        const int32_t* perm = nullptr; int64_t first = 0; const void* st = nullptr;     // the batch's rows (recorded by the batch loads)
+    } moe;
 };
 
 static void add_tensor(dmvae_plan* p, const std::string& name, int64_t off, int rows, int cols, int64_t ld) {
@@ -494,6 +506,67 @@ extern "C" int dmvae_plan_bind(dmvae_plan* p, const dmvae_buffers* b) {
     return 0;
 }
 
+// Mixture-of-experts attachment (models.py:10-163 of the reference).  W_moe goes behind the last weight matrix, the tail (every bias, then
+// the prior tables) moves up behind it, b_moe is appended to the biases; the workspace grows by the MoE buffers.
+extern "C" int dmvae_plan_attach_moe(dmvae_plan* p, const dmvae_moe_config* m) {
+    DMVAE_REQUIRE(p && m, "dmvae_plan_attach_moe: null argument");
+    DMVAE_REQUIRE(!p->bound && !p->moe.on, "dmvae_plan_attach_moe: attach once, before dmvae_plan_bind");
+    if (p->vade || !p->conv.empty() || p->dw_slices_max > 1) {
+        set_error("dmvae_plan_attach_moe: the MoE head runs on DMVAE plans with the MLP trunk and fewer than 8192 rows (VaDE: its gate p(c|z) "
+                  "sends gradients through Z; conv trunk: the flat input is not resident; larger batches: dW K-slices)");
+        return DMVAE_EUNSUPPORTED;
+    }
+    const int E = m->n_experts, O = m->output_dim;
+    DMVAE_REQUIRE(E == p->cfg.n_classes, "dmvae_plan_attach_moe: n_experts %d must equal the gate's n_classes %d", E, p->cfg.n_classes);
+    DMVAE_REQUIRE(E >= 1 && E <= 256 && O >= 1 && O <= 64 && E * O <= 1024, "dmvae_plan_attach_moe: E=%d, O=%d (E <= 256, O <= 64, E*O <= 1024)", E, O);
+    DMVAE_REQUIRE(m->labels && m->label_rows > 0, "dmvae_plan_attach_moe: null labels");
+    auto& M = p->moe;
+    M.cfg = *m;
+    M.EO = E * O; M.EOp = pad64(M.EO);
+    const bool fl = m->featLearn != 0;
+    PLayer& L = M.L;
+    L.name = "moe"; L.in = fl ? p->cfg.latent_dim : p->cfg.input_dim; L.in_pad = fl ? p->Dp : p->Ip; L.out = M.EO; L.out_pad = M.EOp; L.ldw = M.EOp;
+    L.w_off = p->out.w_off + (int64_t)p->out.in_pad * p->out.out_pad;
+    const int64_t tail = align_up(L.w_off + (int64_t)L.in_pad * L.ldw, 4096);
+    const int64_t dt = tail - p->tail_off;                 // every tail tensor moves up by dt; the prior tables by dt + EOp more
+    for (auto& c : p->conv) c.b_off += dt;
+    for (auto& l : p->enc) l.b_off += dt;
+    for (auto& l : p->dec) l.b_off += dt;
+    p->zc.b_off += dt; p->mv.b_off += dt; p->lg.b_off += dt; p->out.b_off += dt;
+    L.b_off = p->prior_off + dt;
+    for (auto& t : p->tensors) {
+        if (t.name[0] == 'b' && t.name[1] == '_') t.offset += dt;
+        else if (!strncmp(t.name, "prior_", 6)) t.offset += dt + M.EOp;
+    }
+    p->tail_off = tail;
+    p->prior_off += dt + M.EOp;
+    p->param_elems += dt + M.EOp;
+    add_tensor(p, "W_moe", L.w_off, L.in, M.EO, L.ldw);
+    add_tensor(p, "b_moe", L.b_off, 1, M.EO, M.EOp);
+    int64_t w = p->work_bytes;
+    auto take = [&](int64_t bytes) { int64_t o = w; w += align_up(bytes, 256); return o; };
+    const int64_t Bp = p->Bp;
+    M.o_P = take(Bp * M.EOp * 4);
+    M.o_dP = take(Bp * M.EOp * p->es);
+    M.o_inp = take(Bp * p->Dp * p->es);
+    M.o_dq = take(Bp * 256 * 4);
+    M.o_pred = take(Bp * 64 * 4);
+    M.nblk = moe_head_nblocks(p->Bp);
+    M.o_part = take((int64_t)M.nblk * 2 * 4);
+    M.o_acc = take(256);
+    p->cs_elems = std::max<int64_t>(p->cs_elems, (int64_t)64 * M.EOp);
+    p->o_cs = take(p->cs_elems * 4);        // (the column-sum scratch, grown if the expert layer is the widest)
+    p->work_bytes = w;
+    M.on = true;
+    return 0;
+}
+
+extern "C" int dmvae_plan_moe_set_labels(dmvae_plan* p, const float* labels, int64_t label_rows) {
+    DMVAE_REQUIRE(p && p->moe.on && labels && label_rows > 0, "dmvae_plan_moe_set_labels: no MoE attachment / null labels");
+    p->moe.cfg.labels = labels; p->moe.cfg.label_rows = label_rows;
+    return 0;
+}
+
 #define WS(p, off) (reinterpret_cast<char*>((p)->buf.work) + (off))
 #define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
@@ -513,6 +586,7 @@ extern "C" int dmvae_plan_load_batch(dmvae_plan* p, void* stream, const float* d
     void* xa = p->cfg.dtype == DMVAE_BF16 ? (void*)XB(p) : nullptr;
     p->tsrc_valid = false;
     p->pf.armed = p->pf.done = false;
+    p->moe.perm = perm; p->moe.first = first; p->moe.st = use_state_cursor ? p->buf.state : nullptr;
     return gather_launch(s, p->cfg.dtype, data, n_rows, p->cfg.input_dim, perm, first, p->cfg.max_batch, n_valid, p->Bp, xa, p->Ip,
                          reinterpret_cast<float*>(WS(p, p->o_xf)), p->Ip, p->Ip, use_state_cursor ? p->buf.state : nullptr);
 }
@@ -532,6 +606,7 @@ extern "C" int dmvae_plan_load_batch_step(dmvae_plan* p, void* stream, const flo
     p->tsrc_valid = true;
     p->tsrc_used = false;
     p->pf.armed = p->pf.done = false;
+    p->moe.perm = perm; p->moe.first = first; p->moe.st = p->tsrc.st;
     if constexpr (MEAS_NO_STEP_GATHER) {      // measurement build 11 only (measure.h): timing of a step without its gather
         static int calls = 0;
         if (++calls > 2) return 0;
@@ -548,6 +623,7 @@ extern "C" int dmvae_plan_prefetch_batch(dmvae_plan* p, const float* data, int64
                                          int use_state_cursor) {
     DMVAE_REQUIRE(p && p->bound && data, "dmvae_plan_prefetch_batch: plan not bound / null data");
     DMVAE_REQUIRE(n_valid >= 0 && n_valid <= p->cfg.max_batch, "dmvae_plan_prefetch_batch: n_valid=%d exceeds max_batch=%d", n_valid, p->cfg.max_batch);
+    if (p->moe.on) { set_error("dmvae_plan_prefetch_batch: not with a MoE attachment (its labels follow the current batch)"); return DMVAE_EUNSUPPORTED; }
     if (!p->tgt_gather || p->o_x2 < 0) { set_error("dmvae_plan_prefetch_batch: this plan assembles its batches with dmvae_plan_load_batch (f32, conv trunk, or an output layer on the macro tile)"); return DMVAE_EUNSUPPORTED; }
     DMVAE_REQUIRE(p->tsrc_valid && !p->tsrc_used, "dmvae_plan_prefetch_batch: no current batch (dmvae_plan_load_batch_step or dmvae_plan_swap_batch first)");
     p->pf.data = data; p->pf.n_rows = n_rows; p->pf.perm = perm; p->pf.first = first; p->pf.n_valid = n_valid;
@@ -774,6 +850,16 @@ extern "C" int dmvae_plan_decode(dmvae_plan* p, void* stream, const float* Z, in
     return fwd_dense(p, s, WS(p, p->o_dec[last]), p->dec[last].out_pad, p->dec[last].out_pad, L, p->Ip, 0, kind, WS(p, p->o_recon), p->Ip);
 }
 
+static int moe_stage(dmvae_plan* p, hipStream_t s, int n_valid, float inv_B, bool backward);
+extern "C" int dmvae_plan_moe_predict(dmvae_plan* p, void* stream, int n_valid) {
+    DMVAE_REQUIRE(p && p->bound && p->moe.on, "dmvae_plan_moe_predict: plan not bound / no MoE attachment");
+    DMVAE_REQUIRE(n_valid > 0 && n_valid <= p->cfg.max_batch, "dmvae_plan_moe_predict: n_valid=%d out of range", n_valid);
+    DMVAE_REQUIRE(!p->tsrc_valid, "dmvae_plan_moe_predict: load the batch with dmvae_plan_load_batch");
+    hipStream_t s = (hipStream_t)stream;
+    TRY(encode_impl(p, s));
+    return moe_stage(p, s, n_valid, 1.f / n_valid, false);
+}
+
 // Split-K of the dW GEMMs: off.  Measured (tools/gemm_sweep.py) fp32-atomic split-K loses on every
 // dW shape of the step except 512x512 (-13 %), so dW is a plain store and the whole step is
 // bit-reproducible; cfg.deterministic is kept in the ABI for a future slab-reduce split-K.
@@ -914,6 +1000,41 @@ static int dx_dense(dmvae_plan* p, hipStream_t s, const void* dY, int64_t ldy, i
     return gemm_plan(p, s, DMVAE_GEMM_DX, N, Kdim, dY, ldy, Wp(p, w_off), ldw, &e, deferred);
 }
 
+// The MoE stage of a pass, behind the latent stage (which has written logits, mean, gmu and dlogits): expert outputs P (a GEMM with the
+// bias epilogue off the batch; featLearn: inside the row kernel), the row kernel (gate, mixture, loss, dP, dlogits / gmu terms), and the
+// expert layer's weight-gradient problem (queued with the others on bf16 plans).
+static int moe_stage(dmvae_plan* p, hipStream_t s, int n_valid, float inv_B, bool backward) {
+    auto& M = p->moe;
+    const dmvae_config& c = p->cfg;
+    const bool fl = M.cfg.featLearn != 0;
+    if (!fl)
+        TRY(fwd_dense(p, s, XB(p), p->Ip, p->Ip, M.L, M.EOp, 0, DMVAE_EPI_BIAS_F32, WS(p, M.o_P), M.EOp));
+    MoeHeadArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = n_valid; a.B_pad = p->Bp; a.E = M.cfg.n_experts; a.O = M.cfg.output_dim;
+    a.featLearn = fl; a.classification = M.cfg.classification != 0; a.backward = backward; a.act_dtype = c.dtype;
+    a.inv_B = inv_B;
+    a.P = reinterpret_cast<float*>(WS(p, M.o_P)); a.ldP = M.EOp;
+    a.logits = reinterpret_cast<const float*>(WS(p, p->o_lg)); a.ld_lg = p->Kp;
+    a.Y = M.cfg.labels; a.n_rows = M.cfg.label_rows;
+    a.perm = M.perm; a.first = M.first; a.batch = c.max_batch; a.st = reinterpret_cast<const dmvae_state*>(M.st);
+    a.mean = reinterpret_cast<const float*>(WS(p, p->o_mv)); a.ld_mean = 2 * p->Dp; a.D = c.latent_dim; a.Dp = p->Dp;
+    a.W = p->buf.param + M.L.w_off; a.ldW = M.L.ldw; a.bias = p->buf.param + M.L.b_off;
+    a.inp_act = WS(p, M.o_inp); a.ld_inp = p->Dp;
+    a.gmu = reinterpret_cast<float*>(WS(p, p->o_gmu)); a.ld_g = p->Dp;
+    a.dP_act = WS(p, M.o_dP); a.ld_dP = M.EOp;
+    a.dlogits_act = WS(p, p->o_dlg); a.ld_dl = p->Kp;
+    a.dq_ws = reinterpret_cast<float*>(WS(p, M.o_dq)); a.ld_dq = 256;
+    a.pred = reinterpret_cast<float*>(WS(p, M.o_pred)); a.ld_pred = 64;
+    a.partials = reinterpret_cast<float*>(WS(p, M.o_part));
+    a.acc = reinterpret_cast<float*>(WS(p, M.o_acc));
+    TRY(moe_head_launch(s, a));
+    if (!backward) return 0;
+    const void* inp = fl ? (const void*)WS(p, M.o_inp) : (const void*)XB(p);
+    const int64_t ldi = fl ? p->Dp : p->Ip;
+    return grad_dense(p, s, inp, ldi, M.L.in_pad, WS(p, M.o_dP), M.EOp, M.EOp, M.L.w_off, M.L.ldw, M.L.b_off);
+}
+
 // stage < 0: the whole forward + backward.  stage 0 / 1 / 2: the three segments after which one
 // contiguous BUCKET of the gradient arena is complete (dmvae_plan_grad_buckets): 0 = forward, loss,
 // decoder backward -> [dec0 .. out, prior tables]; 1 = heads -> [zh|ch, mean|log_var, logits];
@@ -924,6 +1045,7 @@ static int forward_backward_impl(dmvae_plan* p, void* stream, int n_valid, const
     DMVAE_REQUIRE(p && p->bound, "dmvae_plan_forward_backward: plan not bound");
     DMVAE_REQUIRE(n_valid > 0 && n_valid <= p->cfg.max_batch, "dmvae_plan_forward_backward: n_valid=%d out of range", n_valid);
     DMVAE_REQUIRE(stage >= -1 && stage <= 2, "dmvae_plan_forward_backward_stage: stage %d (0, 1, 2)", stage);
+    if (p->moe.on && stage >= 0) { set_error("dmvae_plan_forward_backward_stage: not with a MoE attachment (one rank)"); return DMVAE_EUNSUPPORTED; }
     hipStream_t s = (hipStream_t)stream;
     const dmvae_config& c = p->cfg;
     const int dt = c.dtype;
@@ -944,6 +1066,9 @@ static int forward_backward_impl(dmvae_plan* p, void* stream, int n_valid, const
         p->dw_macro_now = g_dw_macro && p->dw_slices_now > 1;
     }
     const int nd = (int)p->dec.size(), ne = (int)p->enc.size();
+    // dmoe (lossVAE 0): the VAE terms scale their gradients by zero -- exact zeros for the decoder, the z-head and the prior tables,
+    // whose Adam update then moves nothing (m = v = 0 stay 0); the reported VAE loss keeps inv_B
+    const float vae_inv_B = (p->moe.on && !p->moe.cfg.lossVAE) ? 0.f : inv_B;
     auto cso = [](const std::vector<int64_t>& v, int i) -> int64_t { return v.empty() ? -1 : v[i]; };      // column-sum partials of a dY (bf16, Bp % 256 == 0)
     // Loss scalars, Adam t / lr_t and the prior-table gradients need only the forward partials.  Whole pass, bf16:
     // the 1 + 80 blocks of step_finalize ride as extra workgroups of the grouped heads-dX launch further down (one
@@ -1004,7 +1129,7 @@ static int forward_backward_impl(dmvae_plan* p, void* stream, int n_valid, const
     dmvae_latent_args la;
     memset(&la, 0, sizeof(la));
     la.B = n_valid; la.B_pad = p->Bp; la.D = c.latent_dim; la.K = c.n_classes; la.mode = p->vade ? 2 : c.mode; la.act_dtype = dt;
-    la.kl_ratio = 1.f; la.temperature = c.temperature; la.inv_B = inv_B; la.seed = c.seed; la.noise_step = 0;
+    la.kl_ratio = 1.f; la.temperature = c.temperature; la.inv_B = vae_inv_B; la.seed = c.seed; la.noise_step = 0;
     la.mean = reinterpret_cast<float*>(WS(p, p->o_mv)); la.ld_mean = 2 * p->Dp;
     la.log_var = la.mean + p->Dp; la.ld_log_var = 2 * p->Dp;
     la.logits = reinterpret_cast<float*>(WS(p, p->o_lg)); la.ld_logits = p->Kp;
@@ -1040,13 +1165,14 @@ static int forward_backward_impl(dmvae_plan* p, void* stream, int n_valid, const
     } else {
         TRY(latent_launch(s, &la));
     }
+    if (p->moe.on) TRY(moe_stage(p, s, n_valid, inv_B, true));
 
     TRY(decode_hidden(p, s));
     {   // output layer + reconstruction loss + dLoss/dlogits in one epilogue
         const PLayer& L = p->out;
         dmvae_epilogue e;
         memset(&e, 0, sizeof(e));
-        e.kind = DMVAE_EPI_BIAS_RECON; e.m_valid = n_valid; e.n_valid = c.input_dim; e.recon_kind = c.input_type; e.scale = inv_B;
+        e.kind = DMVAE_EPI_BIAS_RECON; e.m_valid = n_valid; e.n_valid = c.input_dim; e.recon_kind = c.input_type; e.scale = vae_inv_B;
         e.out = WS(p, p->o_dl); e.ldo = p->Ip; e.bias = p->buf.param + L.b_off;
         e.aux0 = WS(p, p->o_xf); e.ld0 = p->Ip; e.partials = reinterpret_cast<float*>(WS(p, p->o_rpart));
         const int Kd = p->dec[nd - 1].out_pad;
@@ -1239,6 +1365,9 @@ extern "C" int dmvae_plan_view(const dmvae_plan* p, const char* name, void** ptr
     else if (n == "x") { *ptr = base + p->o_xf; *ld = p->Ip; }
     else if (n == "Z") { *ptr = base + (p->cfg.dtype == DMVAE_BF16 ? p->o_Zf : p->o_Z); *ld = p->Dp; }
     else if (n == "dxlogits") { *ptr = base + p->o_dl; *ld = p->Ip; *dtype = p->cfg.dtype; }
+    else if (n == "moe_P" && p->moe.on) { *ptr = base + p->moe.o_P; *ld = p->moe.EOp; }      // expert outputs (after a training pass: dP, f32)
+    else if (n == "moe_pred" && p->moe.on) { *ptr = base + p->moe.o_pred; *ld = 64; }
+    else if (n == "moe_acc" && p->moe.on) { *ptr = base + p->moe.o_acc; *ld = 4; }
     else if (n == "hzc" && !p->vade) { *ptr = base + p->o_hzc; *ld = 2 * p->Hp; *dtype = p->cfg.dtype; }   // [z-hidden | c-hidden], halves Hp apart
     else if (n.rfind("enc", 0) == 0 && n.size() == 4 && n[3] - '0' < (int)p->enc.size()) {
         const int i = n[3] - '0';

@@ -37,8 +37,15 @@ EXPORTS = [
     "dmvae_plan_create", "dmvae_plan_destroy", "dmvae_plan_sizes", "dmvae_plan_tensor",
     "dmvae_plan_bind", "dmvae_plan_load_batch", "dmvae_plan_load_batch_step", "dmvae_plan_prefetch_batch", "dmvae_plan_swap_batch", "dmvae_plan_forward_backward",
     "dmvae_plan_update", "dmvae_plan_encode", "dmvae_plan_decode", "dmvae_plan_view",
+    "dmvae_plan_attach_moe", "dmvae_plan_moe_set_labels", "dmvae_plan_moe_predict",
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
 ]
+
+
+class MoeConfig(C.Structure):
+    """dmvae_moe_config: the mixture-of-experts attachment of a plan"""
+    _fields_ = [("n_experts", C.c_int32), ("output_dim", C.c_int32), ("featLearn", C.c_int32), ("classification", C.c_int32),
+                ("lossVAE", C.c_int32), ("reserved", C.c_int32), ("labels", C.c_void_p), ("label_rows", C.c_int64)]
 
 
 class Epilogue(C.Structure):
@@ -193,6 +200,9 @@ def _load():
         "dmvae_plan_encode": [vp, vp, i32],
         "dmvae_plan_decode": [vp, vp, vp, i64, i32],
         "dmvae_plan_view": [vp, C.c_char_p, P(vp), P(i64), P(C.c_int32)],
+        "dmvae_plan_attach_moe": [vp, P(MoeConfig)],
+        "dmvae_plan_moe_set_labels": [vp, vp, i64],
+        "dmvae_plan_moe_predict": [vp, vp, i32],
         "dmvae_prof_enable": [i32],
         "dmvae_debug_spin": [vp, i32],
         "dmvae_debug_strip_fwd2": [vp, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64],

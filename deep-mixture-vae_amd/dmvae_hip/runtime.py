@@ -111,7 +111,7 @@ class StepEngine:
     def __init__(self, input_dim, latent_dim, n_classes, enc_layers=(500, 500), head_dim=2000,
                  dec_layers=(2000, 500, 500), input_type="binary", dtype="bf16", max_batch=100,
                  mode="exact", temperature=1.0, seed=0, deterministic=False, session=None,
-                 beta1=0.9, beta2=0.999, adam_eps=1e-8, cnn=False, model="dmvae", adam_ieee=False):
+                 beta1=0.9, beta2=0.999, adam_eps=1e-8, cnn=False, model="dmvae", adam_ieee=False, moe=None):
         self.cnn = bool(cnn)
         self.model = model
         if model not in ("dmvae", "vade"):
@@ -154,6 +154,19 @@ class StepEngine:
         h = C.c_void_p()
         check(lib.dmvae_plan_create(C.byref(cfg), C.byref(h)), "dmvae_plan_create")
         self._plan = h
+        # moe: dict(n_experts, output_dim, featLearn, classification, lossVAE, labels = device f32 [rows, output_dim]):
+        # the mixture-of-experts head of models.py (dmvae_plan_attach_moe), attached before the plan's sizes are read
+        self.moe = None
+        if moe is not None:
+            labels = moe["labels"]
+            assert labels.dtype == torch.float32 and labels.is_contiguous() and labels.dim() == 2 and labels.shape[1] == int(moe["output_dim"])
+            mc = _lib.MoeConfig()
+            mc.n_experts, mc.output_dim = int(moe["n_experts"]), int(moe["output_dim"])
+            mc.featLearn, mc.classification, mc.lossVAE = int(bool(moe["featLearn"])), int(bool(moe["classification"])), int(bool(moe["lossVAE"]))
+            mc.labels, mc.label_rows = labels.data_ptr(), labels.shape[0]
+            check(lib.dmvae_plan_attach_moe(self._plan, C.byref(mc)), "dmvae_plan_attach_moe")
+            self.moe = dict(moe)
+            self._moe_labels = labels               # keep alive
         sz = _lib.Sizes()
         check(lib.dmvae_plan_sizes(self._plan, C.byref(sz)), "dmvae_plan_sizes")
         self.sizes = sz
@@ -260,6 +273,13 @@ class StepEngine:
                 p["b_" + name] = rng.uniform(-lb, lb, size=(fo,))
         p["prior_means"] = rng.randn(self.n_classes, self.latent_dim)
         p["prior_log_vars"] = np.zeros((self.n_classes, self.latent_dim))
+        if self.moe is not None:
+            # regression_weights ~ N(0, 1) (tf.initializers.random_normal, models.py:66-70), drawn from the same stream AFTER the prior
+            # means, as [E][O][in]; regression_biases = 0 (:51-55)
+            E, O = int(self.moe["n_experts"]), int(self.moe["output_dim"])
+            w = rng.randn(E, O, self.latent_dim if self.moe["featLearn"] else self.input_dim)
+            p["W_moe"] = w.transpose(2, 0, 1).reshape(w.shape[2], E * O)
+            p["b_moe"] = np.zeros((E * O,))
         self.param.zero_()
         self.m.zero_()
         self.v.zero_()
@@ -268,6 +288,37 @@ class StepEngine:
         self.set_parameters(p)
         st = self.read_state()
         self.write_state(adam_t=0, noise_step=0, kl_ratio=st.kl_ratio, lr=st.lr)
+
+    # ------------------------------------------------------------ mixture of experts
+    def moe_acc(self):
+        """the attachment's accumulators: [epoch loss_moe sum, epoch error sum, last batch loss_moe, last batch error] (host floats)"""
+        return self._moe_acc_view().cpu().numpy().astype(np.float64)
+
+    def _moe_acc_view(self):
+        p, ld, dt = C.c_void_p(), C.c_int64(), C.c_int32()
+        check(lib.dmvae_plan_view(self._plan, b"moe_acc", C.byref(p), C.byref(ld), C.byref(dt)), "dmvae_plan_view")
+        off = p.value - self.work.data_ptr()
+        return self.work[off: off + 16].view(torch.float32)
+
+    def moe_zero_acc(self):
+        self._moe_acc_view().zero_()
+
+    def moe_set_labels(self, labels):
+        assert labels.dtype == torch.float32 and labels.is_contiguous() and labels.shape[1] == int(self.moe["output_dim"])
+        self._moe_labels = labels
+        check(lib.dmvae_plan_moe_set_labels(self._plan, ptr(labels), labels.shape[0]), "dmvae_plan_moe_set_labels")
+
+    def moe_predict(self, n_valid=None):
+        """forward only on the loaded batch (dmvae_plan_load_batch): fills the "moe_pred" view, adds loss / error to the accumulators"""
+        n_valid = self.max_batch if n_valid is None else int(n_valid)
+        check(lib.dmvae_plan_moe_predict(self._plan, self._stream(), n_valid), "dmvae_plan_moe_predict")
+
+    def moe_reference_parameters(self):
+        """W_moe / b_moe in the reference's shapes: regression_weights [E, O, in], regression_biases [O, E]"""
+        E, O = int(self.moe["n_experts"]), int(self.moe["output_dim"])
+        w = self._to_host(self.param_view("W_moe"), "W_moe")
+        b = self._to_host(self.param_view("b_moe"), "b_moe")
+        return w.reshape(w.shape[0], E, O).transpose(1, 2, 0).copy(), b.reshape(E, O).T.copy()
 
     def refresh_shadow(self):
         self._require_current_master("refresh_shadow")
@@ -556,6 +607,8 @@ class StepEngine:
         t = torch.as_strided(flat, (self.batch_pad, ld.value), (ld.value, 1))
         full_cols = {"mean": self.latent_dim, "log_var": self.latent_dim, "logits": self.n_classes,
                      "weights": self.n_classes, "recon": self.input_dim, "x": self.input_dim,
+                     "moe_pred": self.moe["output_dim"] if self.moe else 0,
+                     "moe_P": self.moe["n_experts"] * self.moe["output_dim"] if self.moe else 0,
                      "Z": self.latent_dim, "dxlogits": self.input_dim}.get(name, ld.value)
         return t[: (self.max_batch if rows is None else rows), : (full_cols if cols is None else cols)]
 

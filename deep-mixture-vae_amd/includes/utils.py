@@ -1,8 +1,8 @@
 """Host-side data utilities of the DMVAE drop-in -- the counterpart of the parts of
 code/includes/utils.py that the hot path touches: sample_gumbel (:17-19),
 get_clustering_accuracy (:22-34), load_data("mnist") (:122-148) and Dataset
-(:428-466).  The MoE label generators, MEDataset and the other loaders are out
-of scope."""
+(:428-466), and for the mixture-of-experts models the label generators (:37-74)
+and MEDataset (:378-425).  The other loaders are out of scope."""
 import gzip
 import math
 import os
@@ -85,7 +85,51 @@ def load_data(datagroup, **args):
         ds.train_data, ds.train_classes = allx[:n_tr], cls[:n_tr]
         ds.test_data, ds.test_classes = allx[n_tr:], cls[n_tr:]
     ds.train_labels = ds.test_labels = None
+    if args.get("moe"):
+        # train.py:146-151 of the reference (MoE models only: the regression labels draw from the global NumPy stream): one-hot
+        # classes, or the regression targets of a random linear expert per class
+        if args.get("classification"):
+            ds.train_labels, ds.test_labels = generate_classification_variables(ds)
+        else:
+            ds.train_labels, ds.test_labels = generate_regression_variable(ds, int(args["output_dim"]))
     return ds
+
+
+def generate_regression_variable(dataset, output_dim):
+    """includes/utils.py:37-59: one random linear expert per class of the dataset, drawn from the global NumPy stream (biases
+    [O, E_d] first, then weights [O, I, E_d]); the label of a row is its own class's expert applied to it."""
+    n_experts = dataset.n_classes
+    input_dim = dataset.train_data.shape[1]
+    biases = np.random.randn(output_dim, n_experts)
+    weights = np.random.randn(output_dim, input_dim, n_experts)
+
+    def labels(X, cls):
+        out = np.empty((len(X), output_dim))
+        for e in range(n_experts):          # (row by class: the reference's [N, O, E_d] tensor is never formed)
+            rows = np.nonzero(np.asarray(cls) == e)[0]
+            out[rows] = X[rows].astype(np.float64) @ weights[:, :, e].T + biases[:, e]
+        return out
+    return labels(dataset.train_data, dataset.train_classes), labels(dataset.test_data, dataset.test_classes)
+
+
+def generate_classification_variables(dataset):
+    """includes/utils.py:62-74: one-hot over the dataset's classes"""
+    eye = np.eye(dataset.n_classes)
+    return eye[np.asarray(dataset.train_classes, dtype=np.int64)], eye[np.asarray(dataset.test_classes, dtype=np.int64)]
+
+
+def get_moe_clustering_accuracy(weights, classes, n_classes):
+    """get_clustering_accuracy for the mixture-of-experts models.  DEVIATION from the reference, which calls
+    get_clustering_accuracy (includes/utils.py:22-34) and sizes its confusion matrix by the number of EXPERTS: with fewer experts
+    than classes (the CLI default, 5 experts on 10 MNIST classes) it raises IndexError at the first evaluation.  Here the matrix is
+    max(E, n_classes) square and the rectangular assignment is solved by scipy's Hungarian solver."""
+    from scipy.optimize import linear_sum_assignment
+    clusters = np.argmax(weights, axis=-1)
+    n = max(weights.shape[1], int(n_classes), int(np.max(classes)) + 1 if len(classes) else 0)
+    d = np.zeros((n, n), dtype=np.int64)
+    np.add.at(d, (clusters, np.asarray(classes, dtype=np.int64)), 1)
+    r, c = linear_sum_assignment(d.max() - d)
+    return d[r, c].sum() / (len(clusters) * 1.0)
 
 
 class Dataset:
@@ -134,6 +178,66 @@ class Dataset:
         key = str(device)
         if key not in self._device:
             self._device[key] = torch.as_tensor(self._rows).to(device)
+        return self._device[key]
+
+    def __len__(self):
+        return self.epoch_len
+
+
+class MEDataset:
+    """includes/utils.py:378-425: (data, classes, labels); NO shuffle at construction, one np.random.permutation per
+    get_batches() (when shuffle), consecutive batches of (X, labels, classes), short last batch.  As Dataset, the rows are not
+    moved: the cumulative row order is kept, and the device copies of the rows and labels are gathered by it on the GPU."""
+
+    def __init__(self, data, batch_size=100, shuffle=True):
+        data, classes, labels = data
+        self._rows = np.ascontiguousarray(np.asarray(data, dtype=np.float32))
+        self._cls = np.copy(classes)
+        self._lbl = np.ascontiguousarray(np.asarray(labels, dtype=np.float32))
+        self.len = len(self._rows)
+        assert len(self._lbl) == self.len and len(self._cls) == self.len
+        self.order = np.arange(self.len)
+        self.batch_size = batch_size
+        self.shuffle = shuffle
+        self.data_dim = self._rows.shape[1]
+        self.epoch_len = int(math.ceil(self.len / batch_size))
+        self._device = {}
+
+    @property
+    def data(self):
+        return self._rows[self.order]
+
+    @property
+    def classes(self):
+        return self._cls[self.order]
+
+    @property
+    def labels(self):
+        return self._lbl[self.order]
+
+    def reshuffle(self):
+        if self.shuffle:
+            self.order = self.order[np.random.permutation(self.len)]
+        return self.order
+
+    def get_batches(self):
+        order = self.reshuffle()
+        for s in range(0, self.len, self.batch_size):
+            o = order[s:s + self.batch_size]
+            yield self._rows[o], self._lbl[o], self._cls[o]
+
+    def device_rows(self, device):
+        import torch
+        key = str(device)
+        if key not in self._device:
+            self._device[key] = torch.as_tensor(self._rows).to(device)
+        return self._device[key]
+
+    def device_labels(self, device):
+        import torch
+        key = "labels:" + str(device)
+        if key not in self._device:
+            self._device[key] = torch.as_tensor(self._lbl).to(device)
         return self._device[key]
 
     def __len__(self):

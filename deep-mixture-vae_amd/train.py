@@ -29,13 +29,13 @@ parser = argparse.ArgumentParser(description="DMVAE training on MI355X (flag nam
 # (flag, type, default, what it does here).  Names and defaults are the reference's CLI contract; the
 # descriptions say what THIS implementation does with each flag.
 _FLAGS = [
-    ("model", str, "dmvae", "model family; only dmvae and vade are built (the MoE families are rejected)"),
+    ("model", str, "dmvae", "model family: dmvae, vade, dmoe (DeepMoE) or dvmoe (DeepVariationalMoE); vademoe is not built"),
     ("model_name", str, "", "directory name under saved-models/<dataset>/ (default: the model family)"),
     ("dataset", str, "mnist", "mnist | fashion-mnist | synthetic (idx files under data/<dataset>/, else a synthetic stand-in)"),
     ("latent_dim", int, 10, "width D of the Gaussian latent z"),
-    ("output_dim", int, 1, "MoE regression target width (accepted, unused: MoE is out of scope)"),
+    ("output_dim", int, 1, "MoE regression target width (classification: the dataset's class count)"),
     ("n_clusters", int, -1, "mixture components K; -1 takes the dataset's class count"),
-    ("n_experts", int, 5, "MoE expert count (accepted, unused)"),
+    ("n_experts", int, 5, "MoE expert count (= the gate's clusters)"),
     ("n_epochs", int, 500, "training epochs"),
     ("pretrain_epochs_vae", int, 200, "epochs of the reconstruction-only pretraining stage"),
     ("pretrain_epochs_prior", int, 200, "epochs of the prior stage (also max_iter of the GMM that seeds the prior tables)"),
@@ -52,13 +52,13 @@ _FLAGS = [
     ("save_epochs", int, 10, "epochs between two --debug stops"),
 ]
 _SWITCHES = [
-    ("classification", "MoE objective switch (accepted, unused)"),
+    ("classification", "MoE objective: classification (one-hot class labels) instead of regression"),
     ("pretrain", "run the two pretraining stages before training"),
     ("kl_annealing", "start the KL weight at 0 and raise it by --anneal_step every --anneal_epochs"),
     ("plotting", "write sampled.png / regenerated.png grids every --plot_epochs"),
     ("debug", "stop in pdb on the first batch every --save_epochs"),
     ("visdom", "accepted; no Visdom server is contacted"),
-    ("featLearn", "MoE feature-learning switch (accepted, unused)"),
+    ("featLearn", "MoE experts read relu(mean) of the gate's VAE instead of X"),
 ]
 for _name, _type, _default, _help in _FLAGS:
     parser.add_argument("--" + _name, type=_type, default=_default, help=_help)
@@ -96,8 +96,10 @@ def main(argv):
     np.random.seed(argv.seed)
 
     model_str, model_name = argv.model, argv.model_name
-    if model_str[-3:] == "moe":
-        raise NotImplementedError("--model %s: only the ELBO path of the clustering VAEs (dmvae, vade) is built (SURVEY.md 2.1, 8)" % model_str)
+    if model_str in ("dmoe", "dvmoe"):
+        return main_moe(argv, world, rank)
+    if model_str == "vademoe":
+        raise NotImplementedError("--model vademoe: its gate p(c|z) sends gradients through Z into the VaDE latent stage (not built)")
     if model_str not in ("dmvae", "vade"):
         raise NotImplementedError
     plotting = argv.plotting and rank == 0 and argv.dataset == "mnist"   # train.py:157-163: plots exist for the image sets
@@ -225,6 +227,69 @@ def main(argv):
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
+    return loss
+
+
+def main_moe(argv, world, rank):
+    """train.py:146-180, 241-245, 295-297 of the reference: the mixture-of-experts models on separate train / test sets"""
+    import models
+    from dmvae_hip import Session
+    from includes.utils import MEDataset
+    if world > 1:
+        raise NotImplementedError("--model %s: MoE models train on one rank" % argv.model)
+    if argv.pretrain:
+        raise NotImplementedError("--pretrain with a MoE model is not built")
+    if argv.cnn:
+        raise NotImplementedError("--cnn with a MoE model: the flat input the experts read is not resident in conv plans")
+    from includes.utils import load_data
+    dataset = load_data(argv.dataset, classification=argv.classification, output_dim=argv.output_dim, moe=True)
+    output_dim = dataset.n_classes if argv.classification else argv.output_dim      # train.py:150-151
+    sess = Session()
+    kw = dict(activation="relu", initializer="xavier", featLearn=argv.featLearn, batch_size=argv.batch_size, dtype=argv.dtype,
+              enc_layers=[int(v) for v in argv.enc_layers.split(",")], head_dim=argv.head_dim,
+              dec_layers=[int(v) for v in argv.dec_layers.split(",")], gumbel=argv.gumbel, temperature=argv.temperature,
+              noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess)
+    name = argv.model_name or argv.model
+    if argv.model == "dmoe":
+        model = models.DeepMoE(name, dataset.input_type, dataset.input_dim, output_dim, argv.n_experts, argv.classification, **kw)
+    else:
+        model = models.DeepVariationalMoE(name, dataset.input_type, dataset.input_dim, argv.latent_dim, output_dim, argv.n_experts,
+                                          argv.classification, **kw)
+    model.build_graph()
+    train_data = MEDataset((dataset.train_data, dataset.train_classes, dataset.train_labels), batch_size=argv.batch_size)
+    test_data = MEDataset((dataset.test_data, dataset.test_classes, dataset.test_labels), batch_size=argv.batch_size)
+    model.define_train_step(argv.init_lr, train_data.epoch_len * argv.decay_epochs, argv.decay_rate)
+    model.path = "saved-models/%s/%s" % (dataset.datagroup, model.name)
+    os.makedirs(model.path + "/model", exist_ok=True)
+    ckpt_path = model.path + "/model/parameters.ckpt"
+    try:
+        with np.load(ckpt_path, allow_pickle=False) as f:
+            model.load_state_dict({k: f[k] for k in f.files})
+        print("Restored", ckpt_path)
+    except (OSError, ValueError, KeyError, RuntimeError, EOFError, zipfile.BadZipFile) as e:
+        print("Could not load trained model" + ("" if isinstance(e, FileNotFoundError) else " (%s: %s)" % (type(e).__name__, e)))
+    maxAcc = -np.inf
+    loss = float("nan")
+    anneal_term = 0.0 if argv.kl_annealing else 1.0
+    for epoch in range(argv.n_epochs):
+        if argv.kl_annealing and (epoch + 1) % argv.anneal_epochs == 0:
+            anneal_term = min(anneal_term + argv.anneal_step, 1.0)
+        loss, batch_acc, loss_cls = model.train_op(sess, train_data, anneal_term)
+        accTrain, accClTrain = model.get_accuracy(sess, train_data)
+        accTest, accClTest = model.get_accuracy(sess, test_data)
+        if accTest > maxAcc:
+            maxAcc = accTest
+            with open(ckpt_path + ".tmp", "wb") as f:
+                np.savez(f, **model.state_dict())
+            os.replace(ckpt_path + ".tmp", ckpt_path)
+        rec = dict(epoch=epoch, loss=float(loss), loss_moe=float(loss_cls), batch_acc=float(batch_acc), acc_train=float(accTrain),
+                   acc_test=float(accTest), acc_clustering_train=float(accClTrain), acc_clustering_test=float(accClTest),
+                   max_acc=float(maxAcc), kl_ratio=float(anneal_term), batch_size=argv.batch_size, dtype=argv.dtype, model=argv.model)
+        with open(argv.model + "_metrics.jsonl", "a") as fl:
+            fl.write(json.dumps(rec) + "\n")
+        print(json.dumps(rec))
+        if math.isnan(loss):
+            raise FloatingPointError("loss is NaN at epoch %d" % epoch)
     return loss
 
 

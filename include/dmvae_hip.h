@@ -432,6 +432,35 @@ int dmvae_plan_decode(dmvae_plan* p, void* stream, const float* Z, int64_t ldz, 
  * returns the device pointer, leading dimension (elements) and dtype. */
 int dmvae_plan_view(const dmvae_plan* p, const char* name, void** ptr, int64_t* ld, int32_t* dtype);
 
+/* ---- mixture-of-experts head on the gate (models.py:10-163 of the reference: DeepMoE = dmoe, DeepVariationalMoE = dvmoe) -----
+ * Attached to a DMVAE plan (MLP trunk, one rank) between dmvae_plan_create and dmvae_plan_sizes / bind.  The gate is the step's
+ * q = softmax(logits) (base_models.py:249, both KL modes), E = n_experts = the plan's n_classes.  Expert input: the batch X (featLearn 0)
+ * or relu(mean) (featLearn 1).  Tensors: "W_moe" [in][E*O] (column e*O + o; the reference's regression_weights[e][o][i] = W_moe[i][e*O+o])
+ * is the LAST weight matrix of the arena and "b_moe" [E*O] (regression_biases[o][e]) the last bias before the prior tables.
+ * Every step of the plan then adds the MoE loss (classification: models.py:83-105,141-144; regression: :106-113,145-146) and its
+ * gradients (scaled by inv_B, not by kl_ratio); lossVAE 0 (dmoe) scales the VAE terms' gradients by zero (loss = loss_moe).
+ * Labels: [label_rows][O] f32 on the device, read through the batch permutation of the last batch load (device cursor included),
+ * so a captured step needs no host argument.  Accumulators: the "moe_acc" view, 4 floats: [0] += loss_moe of every batch,
+ * [1] += its error (classification: wrong rows; regression: mean squared error * O), [2] / [3] = the last batch's; the caller
+ * zeroes them.  Limits: E <= 256, O <= 64, E * O <= 1024 (DMVAE_EINVAL); conv trunk, VaDE, staged backward, prefetched batches and
+ * plans with dW K-slices (>= 8192 rows): DMVAE_EUNSUPPORTED. */
+typedef struct dmvae_moe_config {
+    int32_t n_experts;       /* E: must equal the plan's n_classes      */
+    int32_t output_dim;      /* O                                        */
+    int32_t featLearn;       /* 0: experts read X; 1: relu(mean)         */
+    int32_t classification;  /* 1: softmax experts; 0: regression        */
+    int32_t lossVAE;         /* 1: loss = loss_moe + vae.loss; 0: loss_moe only */
+    int32_t reserved;
+    const float* labels;     /* device [label_rows][O] f32               */
+    int64_t label_rows;
+} dmvae_moe_config;
+int dmvae_plan_attach_moe(dmvae_plan* p, const dmvae_moe_config* cfg);
+/* another label array (e.g. the test set's) for the following steps / predictions (host state only; a captured step keeps its own) */
+int dmvae_plan_moe_set_labels(dmvae_plan* p, const float* labels, int64_t label_rows);
+/* forward only (get_accuracy / predict): encode the loaded batch, experts, gate, mixture; writes the "moe_pred" view [B_pad][O]
+ * (reconstructed_Y_soft / reconstructed_Y) and adds loss and error to the accumulators; no gradient, no state change */
+int dmvae_plan_moe_predict(dmvae_plan* p, void* stream, int n_valid);
+
 /* Measurement and tuning entry points (per-kernel timing for bench.py's roofline leg, probes, tile knobs) are
  * declared in dmvae_hip_debug.h: exported by the same library, not part of the drop-in boundary. */
 int dmvae_abi_version(void);
