@@ -18,7 +18,9 @@ reference's behaviour: batch_size (reference hard-codes 100, train.py:215-216),
 dtype ("bf16" throughput / "fp32" parity), enc_layers / head_dim / dec_layers
 (reference literals 500,500 / 2000 / 2000,500,500), gumbel + temperature
 (Gumbel-Softmax relaxed KL; default off = the live graph),
-noise ("device" Philox | "host" NumPy stream of the reference), seed.
+noise ("device" Philox | "host" NumPy stream of the reference), seed,
+gmm ("host": pretrain_prior fits the prior tables' mixture with sklearn like
+the reference | "device": dmvae_hip.gmm.DiagGMM, a function of (Z, seed)).
 """
 import math
 import os
@@ -129,9 +131,12 @@ class DeepMixtureVAE(VAE):
     def __init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=None, initializer=None,
                  cnn=False, *, batch_size=100, dtype="bf16", enc_layers=(500, 500), head_dim=2000,
                  dec_layers=(2000, 500, 500), gumbel=False, temperature=1.0, noise="device", seed=0,
-                 deterministic=True, session=None):
+                 deterministic=True, session=None, gmm="host"):
         VAE.__init__(self, name, input_type, input_dim, latent_dim, activation=activation, initializer=initializer)
         self.n_classes = n_classes
+        if gmm not in ("host", "device"):
+            raise ValueError("gmm must be 'host' or 'device'")
+        self.gmm = gmm
         # The checked-in reference forces cnn = True (base_models.py:156); the path BASELINE.json names is
         # the MLP branch (:218-226), the default here.  cnn=True builds the checked-in trunk
         # (:176-216): six 3x3 SAME convolutions, three 2x2 SAME max-pools, FullyConnected 2048 -> 500.
@@ -299,6 +304,30 @@ class DeepMixtureVAE(VAE):
                 out[k].append(eng.view(name, n).cpu().numpy().copy())
         return tuple(np.concatenate(o, axis=0) for o in out)
 
+    def encode_means_device(self, X):
+        """The encoder means of X as one [N][latent_dim] f32 device tensor: every batch's "mean" view is copied on the device,
+        nothing returns to the host."""
+        import torch
+        eng = self._engine
+        Z = torch.empty((len(X), self.latent_dim), dtype=torch.float32, device=self._session.device)
+        for s, xb in self._batches(X):
+            n = xb.shape[0]
+            eng.load_batch(xb, None, 0, n)
+            eng.encode(n)
+            Z[s:s + n].copy_(eng.view("mean", n))
+        return Z
+
+    def _fit_prior_on_device(self, X, n_epochs, n_init):
+        """gmm="device": the mixture of pretrain_prior (base_models.py:367-390, 614-646) fitted by dmvae_hip.gmm.DiagGMM on the
+        device-resident encoder means; deterministic in (Z, seed), so the ranks of a data-parallel run obtain identical tables."""
+        from dmvae_hip.gmm import DiagGMM
+        gmm_model = DiagGMM(self.n_classes, max_iter=n_epochs, n_init=n_init, weights_init=np.ones(self.n_classes) / self.n_classes,
+                            seed=self.seed)
+        gmm_model.fit(self.encode_means_device(X))
+        self._engine.set_parameters({"prior_means": gmm_model.means_,
+                                     "prior_log_vars": np.log(gmm_model.covariances_ + 1e-20)})
+        return gmm_model
+
     def decode(self, Z):
         """reconstructed_X for given Z (what visualization.py:83-87 fetches by feeding model.Z)."""
         import torch
@@ -452,7 +481,10 @@ class DeepMixtureVAE(VAE):
         sess = session or self._session
         if not self._restore("prior"):
             print("Could not load trained prior parameters")
-            if n_epochs > 0:
+            if n_epochs > 0 and self.gmm == "device":
+                self._fit_prior_on_device(data.data, n_epochs, n_init=20)
+                self._save("prior")
+            elif n_epochs > 0:
                 from sklearn.mixture import GaussianMixture
                 Z = self.encode(data.data)[0]
                 gmm_model = GaussianMixture(n_components=self.n_classes, covariance_type="diag", max_iter=n_epochs,
@@ -499,12 +531,12 @@ class VaDE(DeepMixtureVAE):
 
     def __init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=None, initializer=None, cnn=False, *,
                  batch_size=100, dtype="bf16", enc_layers=(2000, 500, 500), dec_layers=(500, 500, 2000), noise="device", seed=0,
-                 deterministic=True, session=None):
+                 deterministic=True, session=None, gmm="host"):
         if cnn and tuple(enc_layers) == (2000, 500, 500):
             enc_layers = (128,)            # base_models.py:486: ("fc", {"input_dim": 2048, "output_dim": 128})
         DeepMixtureVAE.__init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=activation, initializer=initializer,
                                 cnn=cnn, batch_size=batch_size, dtype=dtype, enc_layers=enc_layers, head_dim=64, dec_layers=dec_layers,
-                                gumbel=False, temperature=1.0, noise=noise, seed=seed, deterministic=deterministic, session=session)
+                                gumbel=False, temperature=1.0, noise=noise, seed=seed, deterministic=deterministic, session=session, gmm=gmm)
 
     def build_graph(self):
         from dmvae_hip import StepEngine, default_session
@@ -567,7 +599,10 @@ class VaDE(DeepMixtureVAE):
         """base_models.py:611-646: only the GMM initialisation of the prior tables (n_init = 5), no Adam stage."""
         if not self._restore("prior"):
             print("Could not load pretrained prior parameters")
-            if n_epochs > 0:
+            if n_epochs > 0 and self.gmm == "device":
+                self._fit_prior_on_device(data.data, n_epochs, n_init=5)
+                self._save("prior")
+            elif n_epochs > 0:
                 from sklearn.mixture import GaussianMixture
                 Z = self.encode(data.data)[0]
                 gmm_model = GaussianMixture(n_components=self.n_classes, covariance_type="diag", max_iter=n_epochs,

@@ -12,6 +12,7 @@
 
 #include "kernels.h"
 #include "moe_head.h"
+#include "gmm_fit.h"
 #include "measure.h"
 
 namespace dmvae {
@@ -1440,6 +1441,18 @@ extern "C" int dmvae_heads_latent_fwd(void* stream, const dmvae_heads_args* h, c
                   a->glv && a->clv && a->dlogits_act && a->dprior_partials && a->loss_partials, "dmvae_heads_latent_fwd: null pointer");
     DMVAE_REQUIRE(a->ld_Z >= a->D && a->ld_dl >= a->K && a->ld_g >= a->D, "dmvae_heads_latent_fwd: leading dimension too small");
     return heads_latent_launch((hipStream_t)stream, a, h);
+}
+extern "C" int64_t dmvae_gmm_ws_bytes(const dmvae_gmm_config* cfg) {
+    if (int rc = gmm_check(cfg, "dmvae_gmm_ws_bytes")) return rc;
+    return gmm_ws_bytes(cfg);
+}
+extern "C" int dmvae_gmm_fit(void* stream, const dmvae_gmm_config* cfg, const float* X, int64_t ldx, const int32_t* labels, const float* centers,
+                             const float* weights_init, void* ws, int64_t ws_bytes, dmvae_gmm_result* out) {
+    return gmm_fit_launch((hipStream_t)stream, cfg, X, ldx, labels, centers, weights_init, ws, ws_bytes, out, false);
+}
+extern "C" int dmvae_gmm_kmeans(void* stream, const dmvae_gmm_config* cfg, const float* X, int64_t ldx, const float* centers, void* ws,
+                                int64_t ws_bytes, dmvae_gmm_result* out) {
+    return gmm_fit_launch((hipStream_t)stream, cfg, X, ldx, nullptr, centers, nullptr, ws, ws_bytes, out, true);
 }
 extern "C" int dmvae_recon_nblocks(int B_pad, int I_pad) { return recon_nblocks(B_pad, I_pad); }
 extern "C" int dmvae_recon_fwd_bwd(void* stream, int act_dtype, int recon_kind, int B, int B_pad, int I, int I_pad, const float* logits,

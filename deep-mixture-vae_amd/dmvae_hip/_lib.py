@@ -38,6 +38,7 @@ EXPORTS = [
     "dmvae_plan_bind", "dmvae_plan_load_batch", "dmvae_plan_load_batch_step", "dmvae_plan_prefetch_batch", "dmvae_plan_swap_batch", "dmvae_plan_forward_backward",
     "dmvae_plan_update", "dmvae_plan_encode", "dmvae_plan_decode", "dmvae_plan_view",
     "dmvae_plan_attach_moe", "dmvae_plan_moe_set_labels", "dmvae_plan_moe_predict",
+    "dmvae_gmm_ws_bytes", "dmvae_gmm_fit", "dmvae_gmm_kmeans",
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
 ]
 
@@ -46,6 +47,19 @@ class MoeConfig(C.Structure):
     """dmvae_moe_config: the mixture-of-experts attachment of a plan"""
     _fields_ = [("n_experts", C.c_int32), ("output_dim", C.c_int32), ("featLearn", C.c_int32), ("classification", C.c_int32),
                 ("lossVAE", C.c_int32), ("reserved", C.c_int32), ("labels", C.c_void_p), ("label_rows", C.c_int64)]
+
+
+class GmmConfig(C.Structure):
+    """dmvae_gmm_config"""
+    _fields_ = [("N", C.c_int32), ("D", C.c_int32), ("K", C.c_int32), ("n_init", C.c_int32), ("max_iter", C.c_int32),
+                ("kmeans_iter", C.c_int32), ("tol", C.c_float), ("reg_covar", C.c_float), ("flags", C.c_int32)]
+
+
+class GmmResult(C.Structure):
+    """dmvae_gmm_result: device pointers"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "weights", "means", "covariances", "lower_bound", "n_iter", "converged", "best_restart", "lower_bounds", "n_iters",
+        "convergeds", "all_weights", "all_means", "all_covariances", "centers", "labels", "kmeans_iters")]
 
 
 class Epilogue(C.Structure):
@@ -203,6 +217,9 @@ def _load():
         "dmvae_plan_attach_moe": [vp, P(MoeConfig)],
         "dmvae_plan_moe_set_labels": [vp, vp, i64],
         "dmvae_plan_moe_predict": [vp, vp, i32],
+        "dmvae_gmm_ws_bytes": [P(GmmConfig)],
+        "dmvae_gmm_fit": [vp, P(GmmConfig), vp, i64, vp, vp, vp, vp, i64, P(GmmResult)],
+        "dmvae_gmm_kmeans": [vp, P(GmmConfig), vp, i64, vp, vp, i64, P(GmmResult)],
         "dmvae_prof_enable": [i32],
         "dmvae_debug_spin": [vp, i32],
         "dmvae_debug_strip_fwd2": [vp, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64],
@@ -222,6 +239,7 @@ def _load():
     lib.dmvae_last_error.restype = C.c_char_p
     lib.dmvae_latent_ws_bytes.restype = C.c_int64
     lib.dmvae_heads_latent_kslice_floats.restype = C.c_int64
+    lib.dmvae_gmm_ws_bytes.restype = C.c_int64
     lib.dmvae_plan_destroy.restype = None
     got = lib.dmvae_abi_version()
     if got != ABI_VERSION:       # the public structs grew between versions: a mismatched pair would read past them

@@ -75,6 +75,8 @@ parser.add_argument("--temperature", type=float, default=1.0)
 parser.add_argument("--enc_layers", type=str, default="500,500")
 parser.add_argument("--head_dim", type=int, default=2000)
 parser.add_argument("--dec_layers", type=str, default="2000,500,500")
+parser.add_argument("--gmm", type=str, default="host", choices=["host", "device"],
+                    help="--pretrain: fit the prior tables' Gaussian mixture with sklearn on the host (the reference) or with dmvae_hip.gmm.DiagGMM on the device")
 parser.add_argument("--cnn", action="store_true", default=False,
                     help="the checked-in convolutional encoder trunk (base_models.py:156,176-216) instead of the MLP branch")
 
@@ -125,7 +127,7 @@ def main(argv):
             model_name, dataset.input_type, dataset.input_dim, argv.latent_dim, n_clusters,
             activation="relu", initializer="xavier", cnn=argv.cnn,
             batch_size=argv.batch_size // world, dtype=argv.dtype,
-            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess
+            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, gmm=argv.gmm
         ).build_graph()
     else:
         model = base_models.DeepMixtureVAE(
@@ -134,7 +136,7 @@ def main(argv):
             batch_size=argv.batch_size // world, dtype=argv.dtype,
             enc_layers=[int(v) for v in argv.enc_layers.split(",")], head_dim=argv.head_dim,
             dec_layers=[int(v) for v in argv.dec_layers.split(",")], gumbel=argv.gumbel, temperature=argv.temperature,
-            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess
+            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, gmm=argv.gmm
         ).build_graph()
 
     # dmvae trains on train + test rows (train.py:205-213)

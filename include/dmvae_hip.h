@@ -461,6 +461,56 @@ int dmvae_plan_moe_set_labels(dmvae_plan* p, const float* labels, int64_t label_
  * (reconstructed_Y_soft / reconstructed_Y) and adds loss and error to the accumulators; no gradient, no state change */
 int dmvae_plan_moe_predict(dmvae_plan* p, void* stream, int n_valid);
 
+/* ---- diagonal-covariance Gaussian mixture fit (the GMM initialisation of the prior tables, base_models.py:367-390, 614-646:
+ * sklearn.mixture.GaussianMixture(covariance_type="diag")) ------------------------------------------------------------------
+ * EM over X [N][ldx] f32 with n_init restarts side by side in one call; sklearn's semantics:
+ *   E: lp_nk = log w_k - 1/2 [D log 2pi + sum_d log var_kd + sum_d (x_nd - mu_kd)^2 / var_kd], ll_n = logsumexp_k, resp = exp(lp - ll)
+ *   M: nk = sum_n resp + 10 eps, w = nk / sum nk, mu = sum resp x / nk, var = sum resp x^2 / nk - mu^2 + reg_covar
+ *   a restart stops once |lb - lb_prev| < tol (lb = mean_n ll) or after max_iter iterations; the restart with the largest final
+ *   lower bound (the first on ties) is copied to the result.
+ * Each restart starts from hard labels (labels [n_init][N], values in [0, K); the initial weights are weights_init when given) or from
+ * centres (centers [n_init][K][D]): then Lloyd's k-means runs first (at most kmeans_iter iterations; it stops when no label changes or
+ * sum_k ||c'_k - c_k||^2 <= 1e-4 * mean_d Var(X_d)) and its labels start the EM.  Exactly one of labels / centers is given.
+ * No float atomics: per-workgroup partial statistics, added in block order, so two runs agree bit for bit.  The calls enqueue
+ * 2 * (max_iter + kmeans_iter) + O(1) launches and never synchronise; a stopped restart's workgroups return at once.
+ * Limits (tables and a 32-row tile live in LDS): K * D <= 3328, K <= 256 and 4 * (2 K (D + 1) + K + 32 (D + 1) + 32 (K + 1)) + 128 <= 65536
+ * bytes, else DMVAE_EUNSUPPORTED. */
+typedef struct dmvae_gmm_config {
+    int32_t N, D, K;
+    int32_t n_init;          /* restarts R >= 1                                    */
+    int32_t max_iter;        /* EM iterations >= 1                                  */
+    int32_t kmeans_iter;     /* Lloyd iterations (centers given / dmvae_gmm_kmeans) */
+    float tol;               /* EM stopping threshold on the lower bound            */
+    float reg_covar;
+    int32_t flags;           /* reserved: 0                                         */
+} dmvae_gmm_config;
+/* device pointers of the caller; every one may be null except weights / means / covariances / lower_bound / n_iter / converged /
+ * best_restart in dmvae_gmm_fit and centers / labels in dmvae_gmm_kmeans */
+typedef struct dmvae_gmm_result {
+    float* weights;          /* [K]     the selected restart                        */
+    float* means;            /* [K][D]                                              */
+    float* covariances;      /* [K][D]                                              */
+    double* lower_bound;     /* [1]                                                 */
+    int32_t* n_iter;         /* [1]                                                 */
+    int32_t* converged;      /* [1]                                                 */
+    int32_t* best_restart;   /* [1]                                                 */
+    double* lower_bounds;    /* [n_init] per restart                                */
+    int32_t* n_iters;        /* [n_init]                                            */
+    int32_t* convergeds;     /* [n_init]                                            */
+    float* all_weights;      /* [n_init][K]                                         */
+    float* all_means;        /* [n_init][K][D]                                      */
+    float* all_covariances;  /* [n_init][K][D]                                      */
+    float* centers;          /* [n_init][K][D] Lloyd's final centres                */
+    int32_t* labels;         /* [n_init][N]    and the labels of those centres      */
+    int32_t* kmeans_iters;   /* [n_init]                                            */
+} dmvae_gmm_result;
+int64_t dmvae_gmm_ws_bytes(const dmvae_gmm_config* cfg);      /* < 0: an error code */
+int dmvae_gmm_fit(void* stream, const dmvae_gmm_config* cfg, const float* X, int64_t ldx, const int32_t* labels, const float* centers,
+                  const float* weights_init, void* ws, int64_t ws_bytes, dmvae_gmm_result* out);
+/* Lloyd's k-means alone from centers [n_init][K][D]: out->centers, out->labels, out->kmeans_iters */
+int dmvae_gmm_kmeans(void* stream, const dmvae_gmm_config* cfg, const float* X, int64_t ldx, const float* centers, void* ws,
+                     int64_t ws_bytes, dmvae_gmm_result* out);
+
 /* Measurement and tuning entry points (per-kernel timing for bench.py's roofline leg, probes, tile knobs) are
  * declared in dmvae_hip_debug.h: exported by the same library, not part of the drop-in boundary. */
 int dmvae_abi_version(void);
