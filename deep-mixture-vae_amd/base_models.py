@@ -20,7 +20,10 @@ dtype ("bf16" throughput / "fp32" parity), enc_layers / head_dim / dec_layers
 (Gumbel-Softmax relaxed KL; default off = the live graph),
 noise ("device" Philox | "host" NumPy stream of the reference), seed,
 gmm ("host": pretrain_prior fits the prior tables' mixture with sklearn like
-the reference | "device": dmvae_hip.gmm.DiagGMM, a function of (Z, seed)).
+the reference | "device": dmvae_hip.gmm.DiagGMM, a function of (Z, seed)),
+eval ("host": get_accuracy copies every batch's scores back and takes arg-max and
+confusion matrix in NumPy | "device": both on the GPU from the resident rows, one
+small matrix read back per call).
 """
 import math
 import os
@@ -30,7 +33,7 @@ import numpy as np
 
 import priors
 from includes.network import DeepNetwork
-from includes.utils import get_clustering_accuracy
+from includes.utils import accuracy_from_confusion, get_clustering_accuracy
 
 
 class VAE:
@@ -131,12 +134,17 @@ class DeepMixtureVAE(VAE):
     def __init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=None, initializer=None,
                  cnn=False, *, batch_size=100, dtype="bf16", enc_layers=(500, 500), head_dim=2000,
                  dec_layers=(2000, 500, 500), gumbel=False, temperature=1.0, noise="device", seed=0,
-                 deterministic=True, session=None, gmm="host"):
+                 deterministic=True, session=None, gmm="host", eval="host"):
         VAE.__init__(self, name, input_type, input_dim, latent_dim, activation=activation, initializer=initializer)
         self.n_classes = n_classes
         if gmm not in ("host", "device"):
             raise ValueError("gmm must be 'host' or 'device'")
         self.gmm = gmm
+        if eval not in ("host", "device"):
+            raise ValueError("eval must be 'host' or 'device'")
+        self.eval = eval
+        self._eval_perm = None
+        self._eval_calls = 0
         # The checked-in reference forces cnn = True (base_models.py:156); the path BASELINE.json names is
         # the MLP branch (:218-226), the default here.  cnn=True builds the checked-in trunk
         # (:176-216): six 3x3 SAME convolutions, three 2x2 SAME max-pools, FullyConnected 2048 -> 500.
@@ -347,9 +355,35 @@ class DeepMixtureVAE(VAE):
         Z = mean if epsilon is None else mean + np.exp(log_var / 2) * np.asarray(epsilon)
         return self.decode(Z)
 
+    def _device_confusion(self, data, order, R, draws=1, eps=None, counter=0):
+        """eval="device": the [R, R] confusion matrix [cluster][class] of the rows `order` of `data`, built on the GPU
+        (StepEngine.eval_clusters) from the resident rows and classes.  The loop only enqueues -- batch gather, encoder, arg-max
+        and count per batch; the matrix and its error flag come back in ONE copy at the end.  eps: VaDE's host noise, flat on
+        the device, batch after batch as [draws, n, latent_dim]."""
+        import torch
+        eng, dev = self._engine, self._session.device
+        rows, cls = data.device_rows(dev), data.device_classes(dev)
+        t = torch.as_tensor(np.ascontiguousarray(order, dtype=np.int32))
+        if self._eval_perm is None or self._eval_perm.numel() != t.numel():      # (a buffer of its own: the captured step holds _perm)
+            self._eval_perm = torch.empty(t.numel(), dtype=torch.int32, device=dev)
+        self._eval_perm.copy_(t)
+        conf = eng.confusion_buffer(R, dev)
+        b, N, D = eng.max_batch, len(order), self.latent_dim
+        for s in range(0, N, b):
+            n = min(b, N - s)
+            eng.load_batch(rows, self._eval_perm, s, n)
+            e = None if eps is None else eps[draws * D * s: draws * D * (s + n)].view(draws, n, D)
+            eng.eval_clusters(conf, cls, self._eval_perm, s, n, draws=draws, eps=e, counter=counter)
+        return eng.read_confusion(conf)
+
     def get_accuracy(self, session, data):
-        """base_models.py:425-432: logits of every batch -> clustering accuracy."""
+        """base_models.py:425-432: logits of every batch -> clustering accuracy.  eval="device": the arg-max and the
+        confusion matrix are taken on the GPU from the resident rows (no row, logit or noise crosses the host); the same
+        encoder kernels on the same rows, so the matrix -- and the accuracy -- equal the host path's exactly.  Both modes
+        reshuffle, so the global NumPy stream and every later epoch are the same."""
         order = data.reshuffle()               # the reference iterates data.get_batches(), which reshuffles
+        if self.eval == "device":
+            return accuracy_from_confusion(self._device_confusion(data, order, self.n_classes), len(order))
         _, _, logits = self.encode(data._rows[order])
         return get_clustering_accuracy(logits, data._cls[order])
 
@@ -531,12 +565,13 @@ class VaDE(DeepMixtureVAE):
 
     def __init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=None, initializer=None, cnn=False, *,
                  batch_size=100, dtype="bf16", enc_layers=(2000, 500, 500), dec_layers=(500, 500, 2000), noise="device", seed=0,
-                 deterministic=True, session=None, gmm="host"):
+                 deterministic=True, session=None, gmm="host", eval="host"):
         if cnn and tuple(enc_layers) == (2000, 500, 500):
             enc_layers = (128,)            # base_models.py:486: ("fc", {"input_dim": 2048, "output_dim": 128})
         DeepMixtureVAE.__init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=activation, initializer=initializer,
                                 cnn=cnn, batch_size=batch_size, dtype=dtype, enc_layers=enc_layers, head_dim=64, dec_layers=dec_layers,
-                                gumbel=False, temperature=1.0, noise=noise, seed=seed, deterministic=deterministic, session=session, gmm=gmm)
+                                gumbel=False, temperature=1.0, noise=noise, seed=seed, deterministic=deterministic, session=session, gmm=gmm,
+                                eval=eval)
 
     def build_graph(self):
         from dmvae_hip import StepEngine, default_session
@@ -620,7 +655,25 @@ class VaDE(DeepMixtureVAE):
 
     def get_accuracy(self, session, data, k=10):
         """base_models.py:654-670: cluster_probs averaged over k noise draws (the reference's NumPy stream, one
-        sample_reparametrization_variables(n, ["Z"]) per draw over the whole set), then the clustering accuracy."""
+        sample_reparametrization_variables(n, ["Z"]) per draw over the whole set), then the clustering accuracy.
+        eval="device": the encoder runs ONCE over the resident rows and the k draws, their responsibilities, the average and
+        its arg-max are one kernel per batch (StepEngine.eval_clusters).  With noise="host" the k draws come from the same
+        calls in the same order as below and are uploaded: the global NumPy stream ends where the host path leaves it, and the
+        two accuracies differ only on rows whose two largest averaged responsibilities tie to float32 rounding.  With
+        noise="device" the draws are Philox in the kernel (keyed by the plan seed, the count of evaluations of this model, the
+        draw and the row's position): ANOTHER Monte-Carlo estimate than the host path's, and no NumPy draw is consumed, so a
+        run's later shuffles differ from an eval="host" run's."""
+        if self.eval == "device":
+            import torch
+            order, eps = data.order, None
+            N, b = len(order), self._engine.max_batch
+            if self.noise == "host":
+                E = np.stack([np.asarray(self.sample_reparametrization_variables(N, variables=["Z"])[self.epsilon], dtype=np.float32)
+                              for _ in range(k)])                                # [k, N, D], then batch after batch [k, n, D]
+                eps = torch.as_tensor(np.concatenate([E[:, s:s + b].reshape(-1) for s in range(0, N, b)])).to(self._session.device)
+            self._eval_calls += 1
+            d = self._device_confusion(data, order, self.n_classes, draws=k, eps=eps, counter=self._eval_calls)
+            return accuracy_from_confusion(d, N)
         X = data.data
         weights = []
         for _ in range(k):

@@ -13,6 +13,7 @@
 #include "kernels.h"
 #include "moe_head.h"
 #include "gmm_fit.h"
+#include "eval_clusters.h"
 #include "measure.h"
 
 namespace dmvae {
@@ -861,6 +862,37 @@ extern "C" int dmvae_plan_moe_predict(dmvae_plan* p, void* stream, int n_valid) 
     return moe_stage(p, s, n_valid, 1.f / n_valid, false);
 }
 
+// get_accuracy on the device (eval_clusters.hip): the encoder on the loaded batch, then the confusion-matrix count on the logits (DMVAE, with or
+// without a MoE attachment) or on VaDE's averaged responsibilities of `draws` samples (one encoder pass; w goes to the "eval_w" view: the logits
+// buffer, which a VaDE plan allocates and never writes).  Every argument is checked before anything is enqueued.
+extern "C" int dmvae_plan_eval_clusters(dmvae_plan* p, void* stream, int n_valid, const int32_t* classes, int64_t n_rows, const int32_t* perm,
+                                        int64_t first, int draws, const float* eps, int64_t ld_eps, uint64_t eval_counter, int32_t* conf, int R,
+                                        int32_t* err_flag) {
+    DMVAE_REQUIRE(p && p->bound, "dmvae_plan_eval_clusters: plan not bound");
+    DMVAE_REQUIRE(n_valid >= 0 && n_valid <= p->cfg.max_batch, "dmvae_plan_eval_clusters: n_valid=%d exceeds max_batch=%d", n_valid, p->cfg.max_batch);
+    hipStream_t s = (hipStream_t)stream;
+    const dmvae_config& c = p->cfg;
+    const EvalRows rows{classes, n_rows, perm, first, n_valid, conf, R, err_flag};
+    if (!p->vade) {
+        TRY(eval_rows_check(rows, c.n_classes, "dmvae_plan_eval_clusters"));
+        TRY(encode_impl(p, s));
+        return confusion_add_launch(s, reinterpret_cast<const float*>(WS(p, p->o_lg)), p->Kp, c.n_classes, rows);
+    }
+    VadeEvalArgs a;
+    a.rows = rows;
+    a.D = c.latent_dim; a.K = c.n_classes; a.draws = draws;
+    a.mean = reinterpret_cast<const float*>(WS(p, p->o_mv)); a.ld_mean = 2 * p->Dp;
+    a.log_var = a.mean + p->Dp; a.ld_log_var = 2 * p->Dp;
+    a.prior_means = p->buf.param + p->prior_off;
+    a.prior_log_vars = a.prior_means + (int64_t)c.n_classes * c.latent_dim;
+    a.eps = eps; a.ld_eps = ld_eps;
+    a.seed = c.seed; a.counter = eval_counter;
+    a.w = reinterpret_cast<float*>(WS(p, p->o_lg)); a.ld_w = p->Kp;
+    TRY(vade_eval_check(a, "dmvae_plan_eval_clusters"));
+    TRY(encode_impl(p, s));
+    return vade_eval_launch(s, a);
+}
+
 // Split-K of the dW GEMMs: off.  Measured (tools/gemm_sweep.py) fp32-atomic split-K loses on every
 // dW shape of the step except 512x512 (-13 %), so dW is a plain store and the whole step is
 // bit-reproducible; cfg.deterministic is kept in the ABI for a future slab-reduce split-K.
@@ -1362,6 +1394,7 @@ extern "C" int dmvae_plan_view(const dmvae_plan* p, const char* name, void** ptr
     else if (n == "log_var") { *ptr = base + p->o_mv + (int64_t)p->Dp * 4; *ld = 2 * p->Dp; }
     else if (n == "logits") { *ptr = base + p->o_lg; *ld = p->Kp; }
     else if (n == "weights") { *ptr = base + p->o_w; *ld = p->Kp; }
+    else if (n == "eval_w" && p->vade) { *ptr = base + p->o_lg; *ld = p->Kp; }      // dmvae_plan_eval_clusters: the averaged responsibilities
     else if (n == "recon") { *ptr = base + p->o_recon; *ld = p->Ip; }
     else if (n == "x") { *ptr = base + p->o_xf; *ld = p->Ip; }
     else if (n == "Z") { *ptr = base + (p->cfg.dtype == DMVAE_BF16 ? p->o_Zf : p->o_Z); *ld = p->Dp; }
@@ -1453,6 +1486,10 @@ extern "C" int dmvae_gmm_fit(void* stream, const dmvae_gmm_config* cfg, const fl
 extern "C" int dmvae_gmm_kmeans(void* stream, const dmvae_gmm_config* cfg, const float* X, int64_t ldx, const float* centers, void* ws,
                                 int64_t ws_bytes, dmvae_gmm_result* out) {
     return gmm_fit_launch((hipStream_t)stream, cfg, X, ldx, nullptr, centers, nullptr, ws, ws_bytes, out, true);
+}
+extern "C" int dmvae_confusion_add(void* stream, const float* scores, int64_t ld, int n_valid, int K, const int32_t* classes, int64_t n_rows,
+                                   const int32_t* perm, int64_t first, int32_t* conf, int R, int32_t* err_flag) {
+    return confusion_add_launch((hipStream_t)stream, scores, ld, K, EvalRows{classes, n_rows, perm, first, n_valid, conf, R, err_flag});
 }
 extern "C" int dmvae_recon_nblocks(int B_pad, int I_pad) { return recon_nblocks(B_pad, I_pad); }
 extern "C" int dmvae_recon_fwd_bwd(void* stream, int act_dtype, int recon_kind, int B, int B_pad, int I, int I_pad, const float* logits,

@@ -39,6 +39,7 @@ EXPORTS = [
     "dmvae_plan_update", "dmvae_plan_encode", "dmvae_plan_decode", "dmvae_plan_view",
     "dmvae_plan_attach_moe", "dmvae_plan_moe_set_labels", "dmvae_plan_moe_predict",
     "dmvae_gmm_ws_bytes", "dmvae_gmm_fit", "dmvae_gmm_kmeans",
+    "dmvae_confusion_add", "dmvae_plan_eval_clusters",
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
 ]
 
@@ -220,6 +221,8 @@ def _load():
         "dmvae_gmm_ws_bytes": [P(GmmConfig)],
         "dmvae_gmm_fit": [vp, P(GmmConfig), vp, i64, vp, vp, vp, vp, i64, P(GmmResult)],
         "dmvae_gmm_kmeans": [vp, P(GmmConfig), vp, i64, vp, vp, i64, P(GmmResult)],
+        "dmvae_confusion_add": [vp, vp, i64, i32, i32, vp, i64, vp, i64, vp, i32, vp],
+        "dmvae_plan_eval_clusters": [vp, vp, i32, vp, i64, vp, i64, i32, vp, i64, u64, vp, i32, vp],
         "dmvae_prof_enable": [i32],
         "dmvae_debug_spin": [vp, i32],
         "dmvae_debug_strip_fwd2": [vp, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64],

@@ -584,13 +584,63 @@ class StepEngine:
         n_valid = self.max_batch if n_valid is None else int(n_valid)
         check(lib.dmvae_plan_encode(self._plan, self._stream(), n_valid), "dmvae_plan_encode")
 
+    # ------------------------------------------------------------ clustering evaluation on the device
+    @staticmethod
+    def confusion_buffer(R, device):
+        """a zeroed int32 [R * R + 1] device buffer: the confusion matrix [cluster][class] and, behind it, the error flag"""
+        return torch.zeros(int(R) * int(R) + 1, dtype=torch.int32, device=device)
+
+    @staticmethod
+    def _conf_args(conf, classes, perm):
+        R = math.isqrt(conf.numel() - 1)
+        assert conf.dtype == torch.int32 and conf.is_contiguous() and R * R + 1 == conf.numel(), "conf: StepEngine.confusion_buffer(R, device)"
+        assert classes.dtype == torch.int32 and classes.is_contiguous() and classes.dim() == 1
+        assert perm is None or (perm.dtype == torch.int32 and perm.is_contiguous() and perm.numel() == classes.numel())
+        return R, C.c_void_p(conf.data_ptr() + 4 * R * R)
+
+    def eval_clusters(self, conf, classes, perm=None, first=0, n_valid=None, draws=10, eps=None, counter=0):
+        """dmvae_plan_eval_clusters on the batch load_batch assembled (rows perm[first : first + n_valid] of the data set, or
+        first .. without a perm): encoder, then conf[cluster][class] += 1 per row, the cluster being the arg-max of the logits
+        (DMVAE) or of VaDE's responsibilities averaged over `draws` samples of Z (one encoder pass; view "eval_w").  conf:
+        confusion_buffer(R); classes: the data set's int32 classes on the device, unpermuted.  VaDE noise: eps f32
+        [draws, n_valid, latent_dim] on the device, or None: Philox in the kernel, keyed by (seed, counter, draw, first + row).
+        Only enqueues: read_confusion() after the last batch is the one synchronisation."""
+        n_valid = self.max_batch if n_valid is None else int(n_valid)
+        R, flag = self._conf_args(conf, classes, perm)
+        if eps is not None:
+            assert eps.dtype == torch.float32 and eps.is_contiguous() and eps.shape == (int(draws), n_valid, self.latent_dim)
+        check(lib.dmvae_plan_eval_clusters(self._plan, self._stream(), n_valid, ptr(classes), classes.numel(), ptr(perm), int(first),
+                                           int(draws), ptr(eps), self.latent_dim, int(counter) & 0xFFFFFFFFFFFFFFFF, ptr(conf), R, flag),
+              "dmvae_plan_eval_clusters")
+
+    def confusion_add(self, conf, scores, classes, perm=None, first=0, n_valid=None, K=None):
+        """dmvae_confusion_add on a device f32 [rows, >= K] score matrix (e.g. the "logits" view another call has just filled)"""
+        assert scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1
+        n_valid = scores.shape[0] if n_valid is None else int(n_valid)
+        K = scores.shape[1] if K is None else int(K)
+        assert n_valid <= scores.shape[0] and K <= scores.shape[1]
+        R, flag = self._conf_args(conf, classes, perm)
+        check(lib.dmvae_confusion_add(self._stream(), ptr(scores), scores.stride(0), n_valid, K, ptr(classes), classes.numel(), ptr(perm),
+                                      int(first), ptr(conf), R, flag), "dmvae_confusion_add")
+
+    @staticmethod
+    def read_confusion(conf):
+        """the [R, R] int64 matrix on the host (one synchronising copy); raises if a kernel flagged a class outside [0, R) or a
+        permutation entry outside the data set"""
+        host = conf.cpu().numpy()
+        R = math.isqrt(len(host) - 1)
+        if host[-1]:
+            raise IndexError("clustering evaluation on the device: %s" % " and ".join(
+                m for bit, m in ((1, "a class outside [0, %d)" % R), (2, "a permutation entry outside the data set")) if host[-1] & bit))
+        return host[:-1].reshape(R, R).astype(np.int64)
+
     def decode(self, Z):
         assert Z.dtype == torch.float32 and Z.is_contiguous() and Z.shape[1] == self.latent_dim
         check(lib.dmvae_plan_decode(self._plan, self._stream(), ptr(Z), self.latent_dim, Z.shape[0]), "dmvae_plan_decode")
 
     def view(self, name, rows=None, cols=None):
         """torch view of a workspace tensor ("mean", "log_var", "logits", "weights",
-        "recon", "x", "Z", "dxlogits")."""
+        "recon", "x", "Z", "dxlogits"; VaDE: "eval_w", what eval_clusters averaged)."""
         p, ld, dt = C.c_void_p(), C.c_int64(), C.c_int32()
         check(lib.dmvae_plan_view(self._plan, name.encode(), C.byref(p), C.byref(ld), C.byref(dt)), "dmvae_plan_view")
         tdt = torch.bfloat16 if dt.value == _lib.BF16 else torch.float32
@@ -606,7 +656,7 @@ class StepEngine:
         flat = self.work[off: off + self.batch_pad * ld.value * es].view(tdt)
         t = torch.as_strided(flat, (self.batch_pad, ld.value), (ld.value, 1))
         full_cols = {"mean": self.latent_dim, "log_var": self.latent_dim, "logits": self.n_classes,
-                     "weights": self.n_classes, "recon": self.input_dim, "x": self.input_dim,
+                     "weights": self.n_classes, "eval_w": self.n_classes, "recon": self.input_dim, "x": self.input_dim,
                      "moe_pred": self.moe["output_dim"] if self.moe else 0,
                      "moe_P": self.moe["n_experts"] * self.moe["output_dim"] if self.moe else 0,
                      "Z": self.latent_dim, "dxlogits": self.input_dim}.get(name, ld.value)

@@ -18,17 +18,24 @@ def sample_gumbel(shape, eps=1e-20):
     return -np.log(eps - np.log(U + eps))
 
 
-def get_clustering_accuracy(weights, classes):
-    """includes/utils.py:22-34; scipy's Hungarian solver replaces the removed
-    sklearn.utils.linear_assignment_."""
+def accuracy_from_confusion(d, size):
+    """The Hungarian step of includes/utils.py:28-34 on a confusion matrix d[cluster][class] (square, integer counts) of `size`
+    rows: the best one-to-one assignment of clusters to classes; scipy's solver replaces the removed
+    sklearn.utils.linear_assignment_.  Shared by the host evaluation (below) and the device one, which builds d on the GPU."""
     from scipy.optimize import linear_sum_assignment
+    d = np.asarray(d, dtype=np.int64)
+    r, c = linear_sum_assignment(d.max() - d)
+    return d[r, c].sum() / (size * 1.0)
+
+
+def get_clustering_accuracy(weights, classes):
+    """includes/utils.py:22-34."""
     clusters = np.argmax(weights, axis=-1)
     n_classes = weights.shape[1]
     size = len(clusters)
     d = np.zeros((n_classes, n_classes), dtype=np.int64)
     np.add.at(d, (clusters, np.asarray(classes, dtype=np.int64)), 1)
-    r, c = linear_sum_assignment(d.max() - d)
-    return d[r, c].sum() / (size * 1.0)
+    return accuracy_from_confusion(d, size)
 
 
 def synthetic_images(n, dim=784, seed=0, density=0.19):
@@ -123,13 +130,20 @@ def get_moe_clustering_accuracy(weights, classes, n_classes):
     get_clustering_accuracy (includes/utils.py:22-34) and sizes its confusion matrix by the number of EXPERTS: with fewer experts
     than classes (the CLI default, 5 experts on 10 MNIST classes) it raises IndexError at the first evaluation.  Here the matrix is
     max(E, n_classes) square and the rectangular assignment is solved by scipy's Hungarian solver."""
-    from scipy.optimize import linear_sum_assignment
     clusters = np.argmax(weights, axis=-1)
     n = max(weights.shape[1], int(n_classes), int(np.max(classes)) + 1 if len(classes) else 0)
     d = np.zeros((n, n), dtype=np.int64)
     np.add.at(d, (clusters, np.asarray(classes, dtype=np.int64)), 1)
-    r, c = linear_sum_assignment(d.max() - d)
-    return d[r, c].sum() / (len(clusters) * 1.0)
+    return accuracy_from_confusion(d, len(clusters))
+
+
+def _device_classes(ds, device):
+    """the unpermuted int32 classes of a data set, resident next to device_rows (uploaded once)"""
+    import torch
+    key = "classes:" + str(device)
+    if key not in ds._device:
+        ds._device[key] = torch.as_tensor(np.ascontiguousarray(ds._cls, dtype=np.int32)).to(device)
+    return ds._device[key]
 
 
 class Dataset:
@@ -179,6 +193,9 @@ class Dataset:
         if key not in self._device:
             self._device[key] = torch.as_tensor(self._rows).to(device)
         return self._device[key]
+
+    def device_classes(self, device):
+        return _device_classes(self, device)
 
     def __len__(self):
         return self.epoch_len
@@ -232,6 +249,9 @@ class MEDataset:
         if key not in self._device:
             self._device[key] = torch.as_tensor(self._rows).to(device)
         return self._device[key]
+
+    def device_classes(self, device):
+        return _device_classes(self, device)
 
     def device_labels(self, device):
         import torch

@@ -9,15 +9,18 @@ is not reproduced, as for every other initialiser here)."""
 import numpy as np
 
 import base_models
-from includes.utils import get_moe_clustering_accuracy
+from includes.utils import accuracy_from_confusion, get_moe_clustering_accuracy
 
 
 class MoE:
     def __init__(self, name, input_type, input_dim, latent_dim, output_dim, n_experts, classification, activation=None, initializer=None,
                  lossVAE=1, featLearn=1, cnn=False, *, batch_size=100, dtype="bf16", enc_layers=(500, 500), head_dim=2000,
-                 dec_layers=(2000, 500, 500), gumbel=False, temperature=1.0, noise="device", seed=0, session=None):
+                 dec_layers=(2000, 500, 500), gumbel=False, temperature=1.0, noise="device", seed=0, session=None, eval="host"):
         if cnn:
             raise NotImplementedError("MoE with the CNN trunk: the flat input the experts read (featLearn off) is not resident in conv plans")
+        if eval not in ("host", "device"):
+            raise ValueError("eval must be 'host' or 'device'")
+        self.eval = eval
         self.name = name
         self.input_dim, self.latent_dim, self.output_dim = int(input_dim), int(latent_dim), int(output_dim)
         self.input_type = input_type
@@ -148,23 +151,34 @@ class MoE:
 
     def get_accuracy(self, session, data):
         """models.py:115-135: (1 - errors / len, clustering accuracy) for classification, (-sum error / epoch_len, clustering
-        accuracy) for regression.  The clustering accuracy sizes its matrix max(E, n_classes): see get_moe_clustering_accuracy."""
+        accuracy) for regression.  The clustering accuracy sizes its matrix max(E, n_classes): see get_moe_clustering_accuracy.
+        eval="device": the gate's arg-max and the confusion matrix are taken on the GPU behind every moe_predict
+        (StepEngine.confusion_add on the "logits" view) instead of copying each batch's logits to the host; the same matrix."""
         import torch
         eng = self.engine
         rows, labels, perm, order = self._bind(data)
         eng.moe_zero_acc()
         b = eng.max_batch
+        n_classes = int(np.max(data._cls)) + 1
+        device = self.eval == "device"
+        if device:
+            cls_d = data.device_classes(eng.device)
+            conf = eng.confusion_buffer(max(self.n_experts, n_classes), eng.device)
         logits = []
         for s in range(0, data.len, b):
             n = min(b, data.len - s)
             eng.load_batch(rows, perm, s, n)
             eng.moe_predict(n)
-            logits.append(eng.view("logits", n).cpu().numpy().copy())
+            if device:
+                eng.confusion_add(conf, eng.view("logits", n), cls_d, perm, s, n)
+            else:
+                logits.append(eng.view("logits", n).cpu().numpy().copy())
         torch.cuda.synchronize(eng.device)
         error = float(eng.moe_acc()[1])
-        logits = np.concatenate(logits, axis=0)
-        cls = data._cls[order]
-        acc_cl = get_moe_clustering_accuracy(logits, cls, int(np.max(data._cls)) + 1)
+        if device:
+            acc_cl = accuracy_from_confusion(eng.read_confusion(conf), data.len)
+        else:
+            acc_cl = get_moe_clustering_accuracy(np.concatenate(logits, axis=0), data._cls[order], n_classes)
         if self.classification:
             return 1 - error / data.len, acc_cl
         return -error / data.epoch_len, acc_cl

@@ -11,13 +11,15 @@ two figures (regenerated.png, sampled.png) as PNG grids.  --pretrain runs the tw
 pretraining stages of base_models.py:304-423 (recon-only Adam at epsilon = 0,
 GMM-initialised prior tables, latent-loss Adam over the c-head).
 New flags (defaults = reference behaviour): --batch_size, --dtype, --seed,
---host_noise, --gumbel, --temperature, --enc_layers, --head_dim, --dec_layers.
+--host_noise, --gumbel, --temperature, --enc_layers, --head_dim, --dec_layers,
+--gmm, --eval (host | device: where get_accuracy takes its arg-max and confusion matrix).
 """
 import argparse
 import json
 import math
 import os
 import sys
+import time
 import zipfile
 
 import numpy as np
@@ -77,6 +79,9 @@ parser.add_argument("--head_dim", type=int, default=2000)
 parser.add_argument("--dec_layers", type=str, default="2000,500,500")
 parser.add_argument("--gmm", type=str, default="host", choices=["host", "device"],
                     help="--pretrain: fit the prior tables' Gaussian mixture with sklearn on the host (the reference) or with dmvae_hip.gmm.DiagGMM on the device")
+parser.add_argument("--eval", type=str, default="host", choices=["host", "device"],
+                    help="get_accuracy: arg-max and confusion matrix in NumPy from scores copied back per batch (the reference's way) or on the "
+                         "device from the resident rows (one small matrix read back per call)")
 parser.add_argument("--cnn", action="store_true", default=False,
                     help="the checked-in convolutional encoder trunk (base_models.py:156,176-216) instead of the MLP branch")
 
@@ -127,7 +132,7 @@ def main(argv):
             model_name, dataset.input_type, dataset.input_dim, argv.latent_dim, n_clusters,
             activation="relu", initializer="xavier", cnn=argv.cnn,
             batch_size=argv.batch_size // world, dtype=argv.dtype,
-            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, gmm=argv.gmm
+            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, gmm=argv.gmm, eval=argv.eval
         ).build_graph()
     else:
         model = base_models.DeepMixtureVAE(
@@ -136,7 +141,7 @@ def main(argv):
             batch_size=argv.batch_size // world, dtype=argv.dtype,
             enc_layers=[int(v) for v in argv.enc_layers.split(",")], head_dim=argv.head_dim,
             dec_layers=[int(v) for v in argv.dec_layers.split(",")], gumbel=argv.gumbel, temperature=argv.temperature,
-            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, gmm=argv.gmm
+            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, gmm=argv.gmm, eval=argv.eval
         ).build_graph()
 
     # dmvae trains on train + test rows (train.py:205-213)
@@ -185,8 +190,10 @@ def main(argv):
             if argv.kl_annealing and (epoch + 1) % argv.anneal_epochs == 0:
                 anneal_term = min(anneal_term + argv.anneal_step, 1.0)
             loss = model.train_op(sess, train_data, anneal_term)
+            t_eval = time.perf_counter()           # (train_op has synchronised; both get_accuracy modes end in a synchronising read-back)
             accTrain = model.get_accuracy(sess, train_data)
             accTest = model.get_accuracy(sess, test_data)
+            eval_seconds = time.perf_counter() - t_eval
             improved = accTest > maxAcc
             if world > 1:
                 # the branch below holds a COLLECTIVE (sync_master): rank 0 decides and every rank follows.  Each rank scores the same
@@ -212,7 +219,7 @@ def main(argv):
                 sec = ep.pop("seconds", None)
                 rec = dict(epoch=epoch, **ep, images_per_sec=(ep.get("rows", 0) / sec if sec else None), train_seconds=sec,
                            acc_train=float(accTrain), acc_test=float(accTest), max_acc=float(max(maxAcc, accTest) if improved else maxAcc),
-                           world=world, batch_size=argv.batch_size, dtype=argv.dtype, model=model_str)
+                           eval_seconds=eval_seconds, eval=argv.eval, world=world, batch_size=argv.batch_size, dtype=argv.dtype, model=model_str)
                 with open(argv.model + "_metrics.jsonl", "a") as fl:
                     fl.write(json.dumps(rec) + "\n")
             if math.isnan(loss):
@@ -250,7 +257,7 @@ def main_moe(argv, world, rank):
     kw = dict(activation="relu", initializer="xavier", featLearn=argv.featLearn, batch_size=argv.batch_size, dtype=argv.dtype,
               enc_layers=[int(v) for v in argv.enc_layers.split(",")], head_dim=argv.head_dim,
               dec_layers=[int(v) for v in argv.dec_layers.split(",")], gumbel=argv.gumbel, temperature=argv.temperature,
-              noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess)
+              noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, eval=argv.eval)
     name = argv.model_name or argv.model
     if argv.model == "dmoe":
         model = models.DeepMoE(name, dataset.input_type, dataset.input_dim, output_dim, argv.n_experts, argv.classification, **kw)
@@ -277,8 +284,10 @@ def main_moe(argv, world, rank):
         if argv.kl_annealing and (epoch + 1) % argv.anneal_epochs == 0:
             anneal_term = min(anneal_term + argv.anneal_step, 1.0)
         loss, batch_acc, loss_cls = model.train_op(sess, train_data, anneal_term)
+        t_eval = time.perf_counter()
         accTrain, accClTrain = model.get_accuracy(sess, train_data)
         accTest, accClTest = model.get_accuracy(sess, test_data)
+        eval_seconds = time.perf_counter() - t_eval
         if accTest > maxAcc:
             maxAcc = accTest
             with open(ckpt_path + ".tmp", "wb") as f:
@@ -286,7 +295,8 @@ def main_moe(argv, world, rank):
             os.replace(ckpt_path + ".tmp", ckpt_path)
         rec = dict(epoch=epoch, loss=float(loss), loss_moe=float(loss_cls), batch_acc=float(batch_acc), acc_train=float(accTrain),
                    acc_test=float(accTest), acc_clustering_train=float(accClTrain), acc_clustering_test=float(accClTest),
-                   max_acc=float(maxAcc), kl_ratio=float(anneal_term), batch_size=argv.batch_size, dtype=argv.dtype, model=argv.model)
+                   max_acc=float(maxAcc), kl_ratio=float(anneal_term), eval_seconds=eval_seconds, eval=argv.eval, batch_size=argv.batch_size,
+                   dtype=argv.dtype, model=argv.model)
         with open(argv.model + "_metrics.jsonl", "a") as fl:
             fl.write(json.dumps(rec) + "\n")
         print(json.dumps(rec))

@@ -428,7 +428,8 @@ int dmvae_plan_train_step(dmvae_plan* p, void* stream, int n_valid,
  * decode: Z (f32 [n][latent_dim], caller) -> sigmoid/identity reconstruction (f32, workspace) */
 int dmvae_plan_encode(dmvae_plan* p, void* stream, int n_valid);
 int dmvae_plan_decode(dmvae_plan* p, void* stream, const float* Z, int64_t ldz, int n_valid);
-/* workspace views: name in {"mean","log_var","logits","recon","weights","Z","xlogits","x"};
+/* workspace views: name in {"mean","log_var","logits","recon","weights","Z","xlogits","x"} and, on VaDE plans, "eval_w"
+ * (dmvae_plan_eval_clusters);
  * returns the device pointer, leading dimension (elements) and dtype. */
 int dmvae_plan_view(const dmvae_plan* p, const char* name, void** ptr, int64_t* ld, int32_t* dtype);
 
@@ -510,6 +511,29 @@ int dmvae_gmm_fit(void* stream, const dmvae_gmm_config* cfg, const float* X, int
 /* Lloyd's k-means alone from centers [n_init][K][D]: out->centers, out->labels, out->kmeans_iters */
 int dmvae_gmm_kmeans(void* stream, const dmvae_gmm_config* cfg, const float* X, int64_t ldx, const float* centers, void* ws,
                      int64_t ws_bytes, dmvae_gmm_result* out);
+
+/* ---- clustering evaluation (get_accuracy: base_models.py:425-432, 654-670, models.py:115-135; get_clustering_accuracy,
+ * includes/utils.py:22-34) on the device (csrc/eval_clusters.hip) ---------------------------------------------------------
+ * The confusion matrix the Hungarian step is solved on, built where the scores are: conf [R][R] int32, entry [cluster][class],
+ * which the calls ADD INTO (the caller zeroes it once, runs every batch of the set, reads it back once).
+ *   cluster of batch row r = the first index of the largest of its K scores (np.argmax's rule; the scores hold no NaN)
+ *   class of batch row r   = classes[perm ? perm[first + r] : first + r]   (int32 [n_rows]; the indexing of dmvae_plan_load_batch)
+ * Rows >= n_valid count nothing.  A class outside [0, R) counts nothing and sets bit 0 of *err_flag (device int32; the caller
+ * checks it with the matrix), a perm entry outside [0, n_rows) bit 1.  Counts are integer atomics: exact in any order.
+ * 1 <= K <= R <= 4096, 0 <= first, first + n_valid <= n_rows (DMVAE_EINVAL). */
+int dmvae_confusion_add(void* stream, const float* scores, int64_t ld, int n_valid, int K, const int32_t* classes, int64_t n_rows,
+                        const int32_t* perm, int64_t first, int32_t* conf, int R, int32_t* err_flag);
+/* The same for the batch loaded by dmvae_plan_load_batch: dmvae_plan_encode, then
+ *   DMVAE plans (MoE attachment or not): the count on the "logits" view, K = n_classes; draws / eps / eval_counter are ignored;
+ *   VaDE plans: ONE encoder pass, then for j < draws in ascending order Z_j = mean + exp(log_var / 2) eps_j,
+ *     gamma_j = get_cluster_probs(Z_j) (priors.py:91-102), w = (sum_j gamma_j) / draws -- written to the "eval_w" view
+ *     [batch_pad][>= K], rows < n_valid -- and the count on w.  eps: device f32 [draws][n_valid][ld_eps], or NULL: Philox in the
+ *     kernel, eps_j[r][d] = element ((j * n_rows + first + r) * latent_dim + d) of the stream (plan seed, step = eval_counter,
+ *     stream id 2) of dmvae_philox_normal -- a function of the row's position in the evaluated order, not of the batch size.
+ *     1 <= draws <= 1024.  The prior tables live in LDS as in the step's latent stage: the same limit, DMVAE_EUNSUPPORTED. */
+int dmvae_plan_eval_clusters(dmvae_plan* p, void* stream, int n_valid, const int32_t* classes, int64_t n_rows, const int32_t* perm,
+                             int64_t first, int draws, const float* eps, int64_t ld_eps, uint64_t eval_counter, int32_t* conf, int R,
+                             int32_t* err_flag);
 
 /* Measurement and tuning entry points (per-kernel timing for bench.py's roofline leg, probes, tile knobs) are
  * declared in dmvae_hip_debug.h: exported by the same library, not part of the drop-in boundary. */
