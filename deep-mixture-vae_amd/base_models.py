@@ -21,6 +21,8 @@ dtype ("bf16" throughput / "fp32" parity), enc_layers / head_dim / dec_layers
 noise ("device" Philox | "host" NumPy stream of the reference), seed,
 gmm ("host": pretrain_prior fits the prior tables' mixture with sklearn like
 the reference | "device": dmvae_hip.gmm.DiagGMM, a function of (Z, seed)),
+gmm_seeding (with gmm="device": "host" k-means++ in NumPy on a host copy of the
+encoder means | "device": dmvae_gmm_seed on the resident means),
 eval ("host": get_accuracy copies every batch's scores back and takes arg-max and
 confusion matrix in NumPy | "device": both on the GPU from the resident rows, one
 small matrix read back per call).
@@ -134,12 +136,15 @@ class DeepMixtureVAE(VAE):
     def __init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=None, initializer=None,
                  cnn=False, *, batch_size=100, dtype="bf16", enc_layers=(500, 500), head_dim=2000,
                  dec_layers=(2000, 500, 500), gumbel=False, temperature=1.0, noise="device", seed=0,
-                 deterministic=True, session=None, gmm="host", eval="host"):
+                 deterministic=True, session=None, gmm="host", eval="host", gmm_seeding="host"):
         VAE.__init__(self, name, input_type, input_dim, latent_dim, activation=activation, initializer=initializer)
         self.n_classes = n_classes
         if gmm not in ("host", "device"):
             raise ValueError("gmm must be 'host' or 'device'")
         self.gmm = gmm
+        if gmm_seeding not in ("host", "device"):
+            raise ValueError("gmm_seeding must be 'host' or 'device'")
+        self.gmm_seeding = gmm_seeding       # takes effect with gmm="device" only
         if eval not in ("host", "device"):
             raise ValueError("eval must be 'host' or 'device'")
         self.eval = eval
@@ -330,7 +335,7 @@ class DeepMixtureVAE(VAE):
         device-resident encoder means; deterministic in (Z, seed), so the ranks of a data-parallel run obtain identical tables."""
         from dmvae_hip.gmm import DiagGMM
         gmm_model = DiagGMM(self.n_classes, max_iter=n_epochs, n_init=n_init, weights_init=np.ones(self.n_classes) / self.n_classes,
-                            seed=self.seed)
+                            seed=self.seed, seeding=self.gmm_seeding)
         gmm_model.fit(self.encode_means_device(X))
         self._engine.set_parameters({"prior_means": gmm_model.means_,
                                      "prior_log_vars": np.log(gmm_model.covariances_ + 1e-20)})
@@ -565,13 +570,13 @@ class VaDE(DeepMixtureVAE):
 
     def __init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=None, initializer=None, cnn=False, *,
                  batch_size=100, dtype="bf16", enc_layers=(2000, 500, 500), dec_layers=(500, 500, 2000), noise="device", seed=0,
-                 deterministic=True, session=None, gmm="host", eval="host"):
+                 deterministic=True, session=None, gmm="host", eval="host", gmm_seeding="host"):
         if cnn and tuple(enc_layers) == (2000, 500, 500):
             enc_layers = (128,)            # base_models.py:486: ("fc", {"input_dim": 2048, "output_dim": 128})
         DeepMixtureVAE.__init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=activation, initializer=initializer,
                                 cnn=cnn, batch_size=batch_size, dtype=dtype, enc_layers=enc_layers, head_dim=64, dec_layers=dec_layers,
                                 gumbel=False, temperature=1.0, noise=noise, seed=seed, deterministic=deterministic, session=session, gmm=gmm,
-                                eval=eval)
+                                eval=eval, gmm_seeding=gmm_seeding)
 
     def build_graph(self):
         from dmvae_hip import StepEngine, default_session

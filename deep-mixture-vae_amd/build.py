@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "dmvae_hip", "libdmvae_hip.so")
-SOURCES = ["gemm_bf16.hip", "gemm_bf16_256.hip", "gemm_f32.hip", "latent.hip", "latent_mfma.hip", "latent_vade.hip", "elementwise.hip", "conv.hip", "heads_dx.hip", "heads_latent.hip", "strip_fwd2.hip", "moe_head.hip", "gmm_fit.hip", "eval_clusters.hip", "api.hip"]
+SOURCES = ["gemm_bf16.hip", "gemm_bf16_256.hip", "gemm_f32.hip", "latent.hip", "latent_mfma.hip", "latent_vade.hip", "elementwise.hip", "conv.hip", "heads_dx.hip", "heads_latent.hip", "strip_fwd2.hip", "moe_head.hip", "gmm_fit.hip", "gmm_seed.hip", "eval_clusters.hip", "api.hip"]
 # -amdgpu-mfma-vgpr-form: accumulators stay in VGPRs.  Left to its default, hipcc (ROCm 7.2) puts the
 # 4-wave GEMM tiles' accumulators in AGPRs and then shuffles them through v_accvgpr_read/write/mov on
 # every K step (256 such moves against 80 MFMAs in the 128x128 dW loop); no kernel here needs > 256 VGPRs.
@@ -55,7 +55,7 @@ def build(force=False, verbose=True):
 
 
 def build_host_asan(verbose=False):
-    """Host-only build of the same sources with AddressSanitizer + UBSan (hipcc --cuda-host-only: no device code, so
+    """Host-only build of the same sources with AddressSanitizer + UBSan (hipcc --cuda-host-only -fno-gpu-sanitize: no device code, so
     no GPU sanitizer is involved and nothing here runs on a GPU box): build/asan/libdmvae_hip_asan.so.  It exercises the
     host-only parts of the library -- plan creation / arena layout / tensor table / argument checks / tile planner --
     under tests/test_host.py::test_plan_layout_under_address_sanitizer.  Returns (library, asan runtime to LD_PRELOAD)."""
@@ -65,7 +65,7 @@ def build_host_asan(verbose=False):
     os.makedirs(objdir, exist_ok=True)
     out = os.path.join(objdir, "libdmvae_hip_asan.so")
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", h) for h in ("dmvae_hip.h", "dmvae_hip_debug.h")]
-    flags = ["--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-fPIC", "-std=c++17", "-fsanitize=address,undefined",
+    flags = ["--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-fPIC", "-std=c++17", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
              "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined"]
     objs, jobs = [], []
     for src in SOURCES:
@@ -92,7 +92,7 @@ def build_host_asan(verbose=False):
             for sname in syms:
                 f.write('const char %s[32] __attribute__((aligned(4096))) = "__CLANG_OFFLOAD_BUNDLE__";\n' % sname)
         run(["gcc", "-c", "-fPIC", stub, "-o", stub.replace(".c", ".o")])
-        run([hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-shared", "-fPIC", "-fsanitize=address,undefined", "-shared-libsan", "-o", out]
+        run([hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-shared", "-fPIC", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-shared-libsan", "-o", out]
             + objs + [stub.replace(".c", ".o")])
     rt = sorted(glob.glob("/opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so"))
     return out, (rt[-1] if rt else None)

@@ -13,6 +13,7 @@
 #include "kernels.h"
 #include "moe_head.h"
 #include "gmm_fit.h"
+#include "gmm_seed.h"
 #include "eval_clusters.h"
 #include "measure.h"
 
@@ -1487,6 +1488,14 @@ extern "C" int dmvae_gmm_kmeans(void* stream, const dmvae_gmm_config* cfg, const
                                 int64_t ws_bytes, dmvae_gmm_result* out) {
     return gmm_fit_launch((hipStream_t)stream, cfg, X, ldx, nullptr, centers, nullptr, ws, ws_bytes, out, true);
 }
+extern "C" int64_t dmvae_gmm_seed_ws_bytes(const dmvae_gmm_seed_config* cfg) {
+    if (int rc = gmm_seed_check(cfg, "dmvae_gmm_seed_ws_bytes")) return rc;
+    return gmm_seed_ws_bytes(cfg);
+}
+extern "C" int dmvae_gmm_seed(void* stream, const dmvae_gmm_seed_config* cfg, const float* X, int64_t ldx, const float* u, void* ws, int64_t ws_bytes,
+                              float* centers, int32_t* rows) {
+    return gmm_seed_launch((hipStream_t)stream, cfg, X, ldx, u, ws, ws_bytes, centers, rows);
+}
 extern "C" int dmvae_confusion_add(void* stream, const float* scores, int64_t ld, int n_valid, int K, const int32_t* classes, int64_t n_rows,
                                    const int32_t* perm, int64_t first, int32_t* conf, int R, int32_t* err_flag) {
     return confusion_add_launch((hipStream_t)stream, scores, ld, K, EvalRows{classes, n_rows, perm, first, n_valid, conf, R, err_flag});
@@ -1533,6 +1542,10 @@ extern "C" int dmvae_gather_rows(void* stream, int act_dtype, const float* data,
 extern "C" int dmvae_philox_normal(void* stream, float* out, int64_t n, uint64_t seed, uint64_t step, uint32_t sid) {
     DMVAE_REQUIRE(out && n > 0, "dmvae_philox_normal: bad argument");
     return philox_launch((hipStream_t)stream, out, n, seed, step, sid, 0);
+}
+extern "C" int dmvae_philox_uniform(void* stream, float* out, int64_t n, uint64_t seed, uint64_t step, uint32_t sid) {
+    DMVAE_REQUIRE(out && n > 0, "dmvae_philox_uniform: bad argument");
+    return philox_launch((hipStream_t)stream, out, n, seed, step, sid, 2);
 }
 extern "C" int dmvae_philox_gumbel(void* stream, float* out, int64_t n, uint64_t seed, uint64_t step, uint32_t sid) {
     DMVAE_REQUIRE(out && n > 0, "dmvae_philox_gumbel: bad argument");

@@ -211,6 +211,13 @@ __device__ __forceinline__ float philox_gumbel_at(uint64_t seed, uint64_t step, 
     return -__logf(1e-20f - __logf(U));
 }
 
+// uniform in [0,1) on the 2^-24 grid: value idx & 3 of block idx >> 2 (the k-means++ seeding's draws; 0 is a legal draw there)
+__device__ __forceinline__ float philox_uniform_at(uint64_t seed, uint64_t step, uint32_t stream_id, uint64_t idx) {
+    uint32_t r[4];
+    philox_block(seed, step, stream_id, idx >> 2, r);
+    return (float)(r[idx & 3] >> 8) * (1.0f / 16777216.0f);
+}
+
 // ---- host side: errors + launch profiling ----
 namespace dmvae {
 void set_error(const char* fmt, ...);

@@ -456,9 +456,11 @@ int spin_launch(hipStream_t s, int us) {
 }
 
 // ---------------------------------------------------------------- noise + casts
+// gumbel: 0 normal, 1 Gumbel, 2 uniform in [0, 1)
 __global__ __launch_bounds__(256) void philox_kernel(float* out, int64_t n, uint64_t seed, uint64_t step, uint32_t sid, int gumbel) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        out[i] = gumbel ? philox_gumbel_at(seed, step, sid, (uint64_t)i) : philox_normal_at(seed, step, sid, (uint64_t)i);
+        out[i] = gumbel == 2 ? philox_uniform_at(seed, step, sid, (uint64_t)i)
+                             : gumbel ? philox_gumbel_at(seed, step, sid, (uint64_t)i) : philox_normal_at(seed, step, sid, (uint64_t)i);
 }
 int philox_launch(hipStream_t s, float* out, int64_t n, uint64_t seed, uint64_t step, uint32_t sid, int gumbel) {
     int nb = (int)((n + 255) / 256);

@@ -39,6 +39,7 @@ EXPORTS = [
     "dmvae_plan_update", "dmvae_plan_encode", "dmvae_plan_decode", "dmvae_plan_view",
     "dmvae_plan_attach_moe", "dmvae_plan_moe_set_labels", "dmvae_plan_moe_predict",
     "dmvae_gmm_ws_bytes", "dmvae_gmm_fit", "dmvae_gmm_kmeans",
+    "dmvae_gmm_seed_ws_bytes", "dmvae_gmm_seed", "dmvae_philox_uniform",
     "dmvae_confusion_add", "dmvae_plan_eval_clusters",
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
 ]
@@ -61,6 +62,12 @@ class GmmResult(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "weights", "means", "covariances", "lower_bound", "n_iter", "converged", "best_restart", "lower_bounds", "n_iters",
         "convergeds", "all_weights", "all_means", "all_covariances", "centers", "labels", "kmeans_iters")]
+
+
+class GmmSeedConfig(C.Structure):
+    """dmvae_gmm_seed_config"""
+    _fields_ = [("N", C.c_int32), ("D", C.c_int32), ("K", C.c_int32), ("n_init", C.c_int32), ("local_trials", C.c_int32),
+                ("seed", C.c_uint64), ("flags", C.c_int32)]
 
 
 class Epilogue(C.Structure):
@@ -221,6 +228,9 @@ def _load():
         "dmvae_gmm_ws_bytes": [P(GmmConfig)],
         "dmvae_gmm_fit": [vp, P(GmmConfig), vp, i64, vp, vp, vp, vp, i64, P(GmmResult)],
         "dmvae_gmm_kmeans": [vp, P(GmmConfig), vp, i64, vp, vp, i64, P(GmmResult)],
+        "dmvae_gmm_seed_ws_bytes": [P(GmmSeedConfig)],
+        "dmvae_gmm_seed": [vp, P(GmmSeedConfig), vp, i64, vp, vp, i64, vp, vp],
+        "dmvae_philox_uniform": [vp, vp, i64, u64, u64, u32],
         "dmvae_confusion_add": [vp, vp, i64, i32, i32, vp, i64, vp, i64, vp, i32, vp],
         "dmvae_plan_eval_clusters": [vp, vp, i32, vp, i64, vp, i64, i32, vp, i64, u64, vp, i32, vp],
         "dmvae_prof_enable": [i32],
@@ -243,6 +253,7 @@ def _load():
     lib.dmvae_latent_ws_bytes.restype = C.c_int64
     lib.dmvae_heads_latent_kslice_floats.restype = C.c_int64
     lib.dmvae_gmm_ws_bytes.restype = C.c_int64
+    lib.dmvae_gmm_seed_ws_bytes.restype = C.c_int64
     lib.dmvae_plan_destroy.restype = None
     got = lib.dmvae_abi_version()
     if got != ABI_VERSION:       # the public structs grew between versions: a mismatched pair would read past them

@@ -2,9 +2,10 @@
 what `sklearn.mixture.GaussianMixture(covariance_type="diag")` computes for the prior tables' initialisation
 (base_models.py: pretrain_prior), with the restarts side by side in one call and a fit that is a function of (Z, seed) alone.
 
-Only the seeding runs on the host: k-means++ (D^2 sampling) per restart in NumPy from `np.random.RandomState(seed)`.  Lloyd's
-k-means from those centres, the initial M-step of its labels and the EM iterations are HIP kernels (csrc/gmm_fit.hip).
-Nothing here imports sklearn."""
+By default only the seeding runs on the host: k-means++ (D^2 sampling) per restart in NumPy from `np.random.RandomState(seed)`.
+Lloyd's k-means from those centres, the initial M-step of its labels and the EM iterations are HIP kernels (csrc/gmm_fit.hip).
+`seeding="device"` draws the centres on the device as well (dmvae_gmm_seed, csrc/gmm_seed.hip: all restarts in one call, optional
+greedy local trials as sklearn's own seeding, no host copy of Z).  Nothing here imports sklearn."""
 import ctypes as C
 import time
 
@@ -87,6 +88,54 @@ def _stack(a, R, shape, dtype, dev, what):
     return t.contiguous()
 
 
+def sklearn_local_trials(n_clusters):
+    """the number of candidates sklearn's greedy k-means++ draws per centre: 2 + int(ln K)"""
+    return 2 + int(np.log(n_clusters))
+
+
+def kmeans_plusplus_device(Z, n_clusters, n_init=1, seed=0, local_trials=1, u=None, return_trials=False):
+    """k-means++ seeding on the device (dmvae_gmm_seed), n_init restarts side by side, enqueued on the current stream without a
+    synchronisation.  local_trials: 1 plain D^2 sampling, 0 sklearn's 2 + int(ln K) greedy trials, 2..8 that many.  u: the uniforms
+    [n_init][K][T] in [0, 1) (NumPy or tensor), or None: the Philox stream (seed, step 0, stream id 3) of dmvae_philox_uniform.
+    Returns (centers [n_init][K][D] f32, rows [n_init][K] int32) as device tensors; with return_trials also every round's candidate
+    rows [n_init][K][T] (round 0: trial 0, the others -1)."""
+    dev = _device_of(Z)
+    Z = _rows_f32(Z, dev)
+    N, D = Z.shape
+    R, K = int(n_init), int(n_clusters)
+    cfg = _lib.GmmSeedConfig(N=N, D=D, K=K, n_init=R, local_trials=int(local_trials), seed=int(seed), flags=0)
+    nbytes = lib.dmvae_gmm_seed_ws_bytes(C.byref(cfg))
+    if nbytes < 0:
+        check(int(nbytes), "dmvae_gmm_seed_ws_bytes")
+    T = int(local_trials) if local_trials else sklearn_local_trials(K)
+    ud = None
+    if u is not None:
+        ud = (u if isinstance(u, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(u, dtype=np.float32))))
+        ud = ud.to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(ud.shape) != (R, K, T):
+            raise ValueError("u must be [n_init][K][trials] = %s, got %s" % ([R, K, T], list(ud.shape)))
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    centers = torch.empty((R, K, D), dtype=torch.float32, device=dev)
+    rows = torch.empty((R, K), dtype=torch.int32, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        check(lib.dmvae_gmm_seed(stream, C.byref(cfg), Z.data_ptr(), Z.stride(0), None if ud is None else ud.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), centers.data_ptr(), rows.data_ptr()), "dmvae_gmm_seed")
+    if return_trials:
+        return centers, rows, ws[:R * K * T * 4].view(torch.int32).reshape(R, K, T).clone()
+    return centers, rows
+
+
+def philox_uniform(n, seed, step=0, stream_id=3, device=None):
+    """n uniforms in [0, 1) of the Philox stream (seed, step, stream_id) as a device f32 tensor (dmvae_philox_uniform)"""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    out = torch.empty(int(n), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.dmvae_philox_uniform(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), out.data_ptr(), out.numel(), int(seed), int(step),
+                                       int(stream_id)), "dmvae_philox_uniform")
+    return out
+
+
 def kmeans(Z, centers, max_iter=300):
     """Lloyd's k-means on the device from centers [K][D] (or [R][K][D]: R runs side by side).  Returns (centers, labels, n_iter)
     with the restart axis kept only when it was given."""
@@ -103,13 +152,25 @@ def kmeans(Z, centers, max_iter=300):
 
 
 class DiagGMM:
-    """GaussianMixture(covariance_type="diag") on the device.  fit(Z) seeds every restart with k-means++ on a host copy of Z;
+    """GaussianMixture(covariance_type="diag") on the device.  fit(Z) seeds every restart with k-means++: seeding="host" (the
+    default) on a host copy of Z in NumPy, seeding="device" with dmvae_gmm_seed on the resident rows (local_trials as in
+    kmeans_plusplus_device; the seeding and the fit are enqueued back to back: no host copy of Z, no synchronisation in between).
     fit(Z, labels=...) / fit(Z, centers=...) start from the given hard labels ([N] or [R][N]) / centres ([K][D] or [R][K][D])
-    instead (their leading axis then is the number of restarts).  Results under sklearn's names, NumPy float64."""
+    instead (their leading axis then is the number of restarts).  Results under sklearn's names, NumPy float64.
+    time_parts (device seeding only): synchronise after the seeding so that seed_seconds_ and device_seconds_ time the two parts
+    apart; without it seed_seconds_ is None and device_seconds_ spans the seeding and the fit."""
 
-    def __init__(self, n_components, max_iter=100, n_init=1, tol=1e-3, reg_covar=1e-6, weights_init=None, kmeans_iter=300, seed=0):
+    def __init__(self, n_components, max_iter=100, n_init=1, tol=1e-3, reg_covar=1e-6, weights_init=None, kmeans_iter=300, seed=0,
+                 seeding="host", local_trials=1, time_parts=False):
         self.n_components, self.max_iter, self.n_init = int(n_components), int(max_iter), int(n_init)
         self.tol, self.reg_covar, self.kmeans_iter, self.seed = float(tol), float(reg_covar), int(kmeans_iter), int(seed)
+        if seeding not in ("host", "device"):
+            raise ValueError("seeding must be 'host' or 'device'")
+        if int(local_trials) != local_trials or not 0 <= int(local_trials) <= 8:
+            raise ValueError("local_trials must be 0 (sklearn's 2 + int(ln K)) or 1..8")
+        if seeding == "host" and int(local_trials) != 1:
+            raise ValueError("the host seeding is plain D^2 sampling: local_trials needs seeding='device'")
+        self.seeding, self.local_trials, self.time_parts = seeding, int(local_trials), bool(time_parts)
         self.weights_init = None if weights_init is None else np.asarray(weights_init, dtype=np.float32)
         if self.weights_init is not None and self.weights_init.shape != (self.n_components,):
             raise ValueError("weights_init must have n_components entries")
@@ -125,11 +186,24 @@ class DiagGMM:
             raise ValueError("give labels or centers, not both")
         dev = _device_of(Z)
         K = self.n_components
-        t0 = time.perf_counter()
-        if labels is None and centers is None:
-            centers = self.seed_centers(Z)
-        self.seed_seconds_ = time.perf_counter() - t0
-        Zd = _rows_f32(Z, dev)
+        on_device = self.seeding == "device" and labels is None and centers is None
+        wi = None if self.weights_init is None else torch.as_tensor(self.weights_init).to(dev)      # (before the seeding: nothing between it and the fit)
+        if on_device:
+            Zd = _rows_f32(Z, dev)
+            if self.time_parts:
+                torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            centers, _ = kmeans_plusplus_device(Zd, K, n_init=self.n_init, seed=self.seed, local_trials=self.local_trials)
+            self.seed_seconds_ = None
+            if self.time_parts:
+                torch.cuda.synchronize(dev)
+                self.seed_seconds_ = time.perf_counter() - t0
+        else:
+            t0 = time.perf_counter()
+            if labels is None and centers is None:
+                centers = self.seed_centers(Z)
+            self.seed_seconds_ = time.perf_counter() - t0
+            Zd = _rows_f32(Z, dev)
         N, D = Zd.shape
         lab = cen = None
         if labels is not None:
@@ -137,15 +211,16 @@ class DiagGMM:
         else:
             cen = _stack(centers, None, (K, D), torch.float32, dev, "centers")
         R = (lab if lab is not None else cen).shape[0]
-        wi = None if self.weights_init is None else torch.as_tensor(self.weights_init).to(dev)
         cfg = _lib.GmmConfig(N=N, D=D, K=K, n_init=R, max_iter=self.max_iter, kmeans_iter=self.kmeans_iter, tol=self.tol,
                              reg_covar=self.reg_covar, flags=0)
         want = ["weights", "means", "covariances", "lower_bound", "n_iter", "converged", "best_restart", "lower_bounds", "n_iters",
                 "convergeds", "all_weights", "all_means", "all_covariances"]
         if cen is not None:
             want.append("kmeans_iters")
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
+        if not on_device:
+            torch.cuda.synchronize(dev)
+        if not on_device or self.time_parts:
+            t0 = time.perf_counter()
         o = _run("dmvae_gmm_fit", Zd, cfg, lab, cen, wi, want)
         self.device_seconds_ = time.perf_counter() - t0        # _run synchronises before it reads back
         self.weights_ = o["weights"].astype(np.float64)

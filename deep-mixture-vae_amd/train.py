@@ -12,7 +12,8 @@ pretraining stages of base_models.py:304-423 (recon-only Adam at epsilon = 0,
 GMM-initialised prior tables, latent-loss Adam over the c-head).
 New flags (defaults = reference behaviour): --batch_size, --dtype, --seed,
 --host_noise, --gumbel, --temperature, --enc_layers, --head_dim, --dec_layers,
---gmm, --eval (host | device: where get_accuracy takes its arg-max and confusion matrix).
+--gmm, --gmm_seeding (host | device: where --gmm device draws its k-means++ centres),
+--eval (host | device: where get_accuracy takes its arg-max and confusion matrix).
 """
 import argparse
 import json
@@ -79,6 +80,8 @@ parser.add_argument("--head_dim", type=int, default=2000)
 parser.add_argument("--dec_layers", type=str, default="2000,500,500")
 parser.add_argument("--gmm", type=str, default="host", choices=["host", "device"],
                     help="--pretrain: fit the prior tables' Gaussian mixture with sklearn on the host (the reference) or with dmvae_hip.gmm.DiagGMM on the device")
+parser.add_argument("--gmm_seeding", type=str, default="host", choices=["host", "device"],
+                    help="--gmm device: k-means++ seeding in NumPy on a host copy of the encoder means, or on the device (dmvae_gmm_seed)")
 parser.add_argument("--eval", type=str, default="host", choices=["host", "device"],
                     help="get_accuracy: arg-max and confusion matrix in NumPy from scores copied back per batch (the reference's way) or on the "
                          "device from the resident rows (one small matrix read back per call)")
@@ -132,7 +135,7 @@ def main(argv):
             model_name, dataset.input_type, dataset.input_dim, argv.latent_dim, n_clusters,
             activation="relu", initializer="xavier", cnn=argv.cnn,
             batch_size=argv.batch_size // world, dtype=argv.dtype,
-            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, gmm=argv.gmm, eval=argv.eval
+            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, gmm=argv.gmm, eval=argv.eval, gmm_seeding=argv.gmm_seeding
         ).build_graph()
     else:
         model = base_models.DeepMixtureVAE(
@@ -141,7 +144,7 @@ def main(argv):
             batch_size=argv.batch_size // world, dtype=argv.dtype,
             enc_layers=[int(v) for v in argv.enc_layers.split(",")], head_dim=argv.head_dim,
             dec_layers=[int(v) for v in argv.dec_layers.split(",")], gumbel=argv.gumbel, temperature=argv.temperature,
-            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, gmm=argv.gmm, eval=argv.eval
+            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, gmm=argv.gmm, eval=argv.eval, gmm_seeding=argv.gmm_seeding
         ).build_graph()
 
     # dmvae trains on train + test rows (train.py:205-213)

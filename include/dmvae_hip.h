@@ -280,6 +280,8 @@ int dmvae_gather_rows(void* stream, int act_dtype, const float* data, int64_t n_
 /* ---- noise (np.random.randn / sample_gumbel, priors.py:67-68,157-158) ---- */
 int dmvae_philox_normal(void* stream, float* out, int64_t n, uint64_t seed, uint64_t step, uint32_t stream_id);
 int dmvae_philox_gumbel(void* stream, float* out, int64_t n, uint64_t seed, uint64_t step, uint32_t stream_id);
+/* uniform in [0, 1): (x >> 8) * 2^-24 of the stream's 32-bit words, word i & 3 of Philox block i >> 2 (the draws of dmvae_gmm_seed) */
+int dmvae_philox_uniform(void* stream, float* out, int64_t n, uint64_t seed, uint64_t step, uint32_t stream_id);
 
 /* ---- casts ---- */
 int dmvae_cast_f32_to_bf16(void* stream, const float* in, void* out, int64_t n);
@@ -511,6 +513,32 @@ int dmvae_gmm_fit(void* stream, const dmvae_gmm_config* cfg, const float* X, int
 /* Lloyd's k-means alone from centers [n_init][K][D]: out->centers, out->labels, out->kmeans_iters */
 int dmvae_gmm_kmeans(void* stream, const dmvae_gmm_config* cfg, const float* X, int64_t ldx, const float* centers, void* ws,
                      int64_t ws_bytes, dmvae_gmm_result* out);
+
+/* ---- k-means++ seeding of those centres on the device (csrc/gmm_seed.hip; Arthur & Vassilvitskii 2007, and the greedy form of
+ * sklearn's _kmeans_plusplus), n_init restarts side by side --------------------------------------------------------------------
+ * With T trials per centre (local_trials: 1 = plain D^2 sampling, 0 = sklearn's T = 2 + int(ln K), 2..8 = that many) and the uniforms
+ * u [n_init][K][T] in [0, 1):
+ *   centre 0 of restart r is row min(floor(u[r][0][0] * N), N - 1);  d2_n = ||x_n - c_0||^2 (f32 differences, summed over d ascending)
+ *   centre k >= 1: tot = sum_n d2_n (f64, workgroup partials added in block order); candidate t is the first row whose f64 running
+ *     sum of d2 (rows in order) exceeds u[r][k][t] * tot, never a row with d2 = 0 (tot not > 0: row min(floor(u * N), N - 1));
+ *     the candidate with the smallest potential sum_n min(d2_n, ||x_n - cand_t||^2) is kept (the first on ties, as argmin), then
+ *     d2_n = min(d2_n, ||x_n - c_k||^2).
+ * u == NULL: u[i] = element i of the Philox stream (seed, step 0, stream id 3) of dmvae_philox_uniform.
+ * centers [n_init][K][D] receive the chosen rows of X bit for bit, rows [n_init][K] (may be NULL) their indices.  After the call the first
+ * n_init * K * T int32 of the workspace hold every round's candidate rows [n_init][K][T] (round 0: trial 0 only, the others -1).
+ * No float atomics and no host synchronisation: 2 launches per centre with T = 1, else 2 + 3 (K - 1), all enqueued up front.
+ * DMVAE_EINVAL: N, D, K, n_init < 1, K > N, local_trials outside 0..8, flags != 0, a workspace too small.  DMVAE_EUNSUPPORTED: T > 8
+ * (local_trials = 0 with K >= 1097) or 4 * T * D + 4096 > 65536 bytes of LDS (the T candidate rows are staged there). */
+typedef struct dmvae_gmm_seed_config {
+    int32_t N, D, K;
+    int32_t n_init;          /* restarts R >= 1                                     */
+    int32_t local_trials;    /* 0: 2 + int(ln K); 1..8                              */
+    uint64_t seed;           /* of the Philox stream when u is NULL                 */
+    int32_t flags;           /* reserved: 0                                         */
+} dmvae_gmm_seed_config;
+int64_t dmvae_gmm_seed_ws_bytes(const dmvae_gmm_seed_config* cfg);      /* < 0: an error code */
+int dmvae_gmm_seed(void* stream, const dmvae_gmm_seed_config* cfg, const float* X, int64_t ldx, const float* u, void* ws, int64_t ws_bytes,
+                   float* centers, int32_t* rows);
 
 /* ---- clustering evaluation (get_accuracy: base_models.py:425-432, 654-670, models.py:115-135; get_clustering_accuracy,
  * includes/utils.py:22-34) on the device (csrc/eval_clusters.hip) ---------------------------------------------------------
