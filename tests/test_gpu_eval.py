@@ -4,6 +4,8 @@ itself (Philox noise fed back).  Counts are integers: no tolerance.  The average
 engine's own `weights` view on an fp32 VaDE plan (tests/test_gpu_vade.py: atol 2e-5); the arg-max may differ from the
 oracle's only where the oracle's two largest entries are closer than 10 x that bar."""
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -12,6 +14,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import dmvae_oracle as O
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+
+import philox_oracle as PH      # noqa: E402
 
 W_ATOL = 2e-5             # tests/test_gpu_vade.py:131
 GAP = 10 * W_ATOL
@@ -180,6 +186,8 @@ def test_vade_eval_philox_noise_fed_back_is_bit_identical():
     L.check(L.lib.dmvae_philox_normal(stream(), L.ptr(z), z.numel(), int(eng._cfg.seed), 7, 2), "dmvae_philox_normal")
     eps = z.view(k, N, D)[:, first:first + n].contiguous()
     assert abs(float(eps.mean())) < 0.1 and abs(float(eps.std()) - 1.0) < 0.1
+    # ... and that buffer is what the exact Philox oracle says stream (seed, counter, 2) holds (atol as in tests/test_gpu_philox.py)
+    np.testing.assert_allclose(z.view(k, N, D).cpu().numpy(), PH.eps_eval(int(eng._cfg.seed), 7, k, N, D), rtol=0, atol=1e-3)
     wf, cf = run(99, eps)
     assert torch.equal(wf, w7) and np.array_equal(cf, c7)
 

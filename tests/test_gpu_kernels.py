@@ -2,6 +2,8 @@
 (ctypes) and compared with the oracle / float64 math on the same inputs."""
 import ctypes as C
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -10,6 +12,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import dmvae_oracle as O
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+
+import philox_oracle as PH      # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -287,7 +293,7 @@ def test_gemm_rejects_unaligned_shapes(hip):
 
 
 # ------------------------------------------------------------------ latent kernel
-def run_latent(L, mean, log_var, logits, eps, gumbel, pm, plv, mode, tau, kl_ratio, act_dtype, B_pad=None, ldpad=0, mfma=False):
+def run_latent(L, mean, log_var, logits, eps, gumbel, pm, plv, mode, tau, kl_ratio, act_dtype, B_pad=None, ldpad=0, mfma=False, seed=1234, noise_step=7):
     B, D = mean.shape
     K = logits.shape[1]
     B_pad = B_pad or ((B + 63) // 64 * 64)
@@ -316,7 +322,7 @@ def run_latent(L, mean, log_var, logits, eps, gumbel, pm, plv, mode, tau, kl_rat
     lp = torch.zeros((nblk, 2), dtype=torch.float32, device="cuda")
     a = L.LatentArgs()
     a.B, a.B_pad, a.D, a.K, a.mode, a.act_dtype = B, B_pad, D, K, mode, act_dtype
-    a.kl_ratio, a.temperature, a.inv_B, a.seed, a.noise_step = kl_ratio, tau, 1.0 / B, 1234, 7
+    a.kl_ratio, a.temperature, a.inv_B, a.seed, a.noise_step = kl_ratio, tau, 1.0 / B, seed, noise_step
     a.mean, a.ld_mean = L.ptr(t["mean"]).value, ldD
     a.log_var, a.ld_log_var = L.ptr(t["log_var"]).value, ldD
     a.logits, a.ld_logits = L.ptr(t["logits"]).value, ldK
@@ -398,7 +404,8 @@ def test_latent_fwd_matches_oracle(hip, mode, shape):
 def test_latent_mfma_form_matches_oracle(hip, shape, noise):
     """K * D >= 4096, exact mode: the contractions as three f32 MFMA GEMMs between two row kernels.  Same oracle, same
     tolerances as the one-kernel form (the expanded squares are computed in exact f32); with device noise the drawn
-    epsilon is recovered from Z and fed to the oracle."""
+    epsilon is recovered from Z, held to the exact Philox oracle (tests/helpers/philox_oracle.py: the draw itself is checked, not only
+    what the kernel makes of it; atol 1e-3 as in tests/test_gpu_philox.py) and fed to the oracle."""
     L = hip
     B, D, K = shape
     rng = np.random.RandomState(B + D + K)
@@ -412,6 +419,7 @@ def test_latent_mfma_form_matches_oracle(hip, shape, noise):
     if noise == "device":
         eps = (g["Zf"][:B].astype(np.float64) - mean) / np.exp(lv / 2)
         assert abs(eps.mean()) < 0.05 and abs(eps.std() - 1.0) < 0.05
+        np.testing.assert_allclose(eps, PH.eps_mfma(1234, 7, B, D), rtol=0, atol=1e-3)
         g2 = run_latent(L, mean, lv, logits, None, None, pm, plv, 0, 1.0, 0.6, 0, ldpad=4, mfma=True)
         np.testing.assert_array_equal(g["Zf"], g2["Zf"])           # same (seed, step) -> same draw
     o = oracle_latent(mean, lv, logits, eps, None, pm, plv, 0, 1.0, 0.6)
@@ -468,8 +476,10 @@ def test_latent_bf16_outputs_and_device_noise(hip):
     np.testing.assert_array_equal(g1["Z"], g2["Z"])            # same (seed, step) -> same noise
     epsd = (g1["Zf"][:B] - mean) / np.exp(lv / 2)              # recover the Philox normals
     assert abs(epsd.mean()) < 0.02 and abs(epsd.std() - 1.0) < 0.02
+    np.testing.assert_allclose(epsd, PH.eps_one_kernel(1234, 7, B, D, K), rtol=0, atol=1e-3)     # ... which are the exact oracle's draws
     # four draws share one Philox block (two Box-Muller pairs): still i.i.d. N(0,1)
     z0 = run_latent(L, np.zeros((2048, 64)), np.zeros((2048, 64)), rng.randn(2048, K), None, None, pm, plv, 0, 1.0, 1.0, 0)["Zf"][:2048]
+    np.testing.assert_allclose(z0, PH.eps_one_kernel(1234, 7, 2048, 64, K), rtol=0, atol=1e-3)
     assert abs(z0.mean()) < 0.01 and abs(z0.std() - 1.0) < 0.01
     assert abs((z0 ** 3).mean()) < 0.03 and abs((z0 ** 4).mean() - 3.0) < 0.1
     assert len(np.unique(z0.round(6))) > 0.95 * z0.size > 0                     # no block reused across rows / lanes
