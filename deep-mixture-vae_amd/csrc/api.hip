@@ -728,6 +728,39 @@ static int conv_dw_split(int64_t K, int tiles) {
     return 1;
 }
 
+// Weight and bias gradient of ONE conv-mode layer (every convolution but the first): dW[kdim][cout_np] = X_patches^T dY, db = column sums of dY,
+// over M padded pixel rows.  sp = 1: fp32 atomics into dW / db, which the caller has zeroed.  sp > 1: K slice y stores its partial product (and
+// bias-gradient partial) into slab y of `slab` (sp * (kdim + 1) * cout_np floats); the slabs are then added in ascending order: bit-reproducible,
+// no float atomics (the atomic form drifts after a few Adam steps).  Rows past the ninth tap are padding (the GEMM fills them with a copy of
+// tap 8) and are zeroed last.  Called by conv_trunk_backward and by dmvae_debug_conv_dw (tests/test_gpu_conv_kernels.py).
+static int conv_layer_dw(hipStream_t s, int dt, int M, int P, int cin, int kdim, const void* in, int64_t cin_ld, const void* dact, int64_t cout_ld,
+                         int cout_np, int cout, int sp, float* slab, float* dW, float* db) {
+    dmvae_epilogue e;
+    memset(&e, 0, sizeof(e));
+    e.kind = DMVAE_EPI_ATOMIC_F32; e.ldo = cout_np; e.n_valid = cout;
+    e.out = dW; e.out2 = db;
+    if (sp > 1) {
+        const int64_t wn = (int64_t)kdim * cout_np;
+        e.kind = DMVAE_EPI_STORE_F32; e.out = slab; e.out2 = slab + (int64_t)sp * wn;
+        GemmArgs g;
+        TRY(gemm_checked(s, dt, DMVAE_GEMM_DW, kdim, cout_np, M, in, cin_ld, dact, cout_ld, &e, 1, &g, P, cin));
+        g.k_split = M / sp; g.slab_stride = wn; g.slab_stride2 = cout_np;
+        if (dt == DMVAE_BF16) TRY(gemm_bf16_dispatch(s, DMVAE_GEMM_DW, g, sp));
+        else {
+            ProfScope ps(s, "gemm_f32_dw", 2.0 * g.M * g.N * (double)g.K, 4.0 * ((double)g.M * g.K + (double)g.K * g.N + (double)g.M * g.N));
+            TRY(gemm_f32_dispatch(s, DMVAE_GEMM_DW, g, sp));
+        }
+        TRY(slab_reduce_launch(s, slab, wn, sp, wn, dW));
+        TRY(slab_reduce_launch(s, slab + (int64_t)sp * wn, cout_np, sp, cout_np, db));
+    } else
+    TRY(gemm_checked(s, dt, DMVAE_GEMM_DW, kdim, cout_np, M, in, cin_ld, dact, cout_ld, &e, sp, nullptr, P, cin));
+    if (kdim > 9 * cin) {
+        const hipError_t me = hipMemsetAsync(dW + (int64_t)9 * cin * cout_np, 0, (size_t)(kdim - 9 * cin) * cout_np * 4, s);
+        if (me != hipSuccess) { set_error("conv gradient pad memset: %s", hipGetErrorString(me)); return (int)me; }
+    }
+    return 0;
+}
+
 // CNN trunk backward from d_flat (gradient of the flattened pool output).  Per layer, last to first:
 //   un-pool + ReLU gate (maxpool2_bwd_relu)  ->  dY, zero-bordered;
 //   dW: ONE DW-layout GEMM with M = (tap, channel): a tile row reads the layer's input shifted by its tap's row
@@ -748,9 +781,6 @@ static int conv_trunk_backward(dmvae_plan* p, hipStream_t s) {
             const void* dpool = last ? (const void*)WS(p, p->o_dflat) : (const void*)rows0(p, L.o_dpool, Po, L.cout_ld);
             TRY(maxpool2_bwd_relu_launch(s, dt, rows0(p, L.o_act, L.P, L.cout_ld), dpool, L.hw, L.cout_ld, p->Bp, dact, last ? 0 : 1));
         }
-        dmvae_epilogue e;
-        memset(&e, 0, sizeof(e));
-        e.kind = DMVAE_EPI_ATOMIC_F32; e.ldo = L.cout_np; e.n_valid = L.cout;
         if (i == 0) {
             TRY(conv_first_dw_launch(s, dt, WS(p, p->o_x), p->Ip, L.hw, p->Bp, dact, L.cout_ld, L.cout, p->buf.grad + L.w_off, L.cout_np, p->buf.grad + L.b_off,
                                      reinterpret_cast<float*>(WS(p, p->o_c0part))));
@@ -758,31 +788,10 @@ static int conv_trunk_backward(dmvae_plan* p, hipStream_t s) {
         }
         const PConv& Lp = p->conv[i - 1];
         const char* in = Lp.pool ? rows0(p, Lp.o_pool, L.P, L.cin_ld) : rows0(p, Lp.o_act, L.P, L.cin_ld);
-        e.out = p->buf.grad + L.w_off; e.out2 = p->buf.grad + L.b_off;
-        const int sp = conv_dw_split(M, (L.kdim / 64) * (L.cout_np / 64));
-        if (sp > 1) {
-            // K slice y stores its partial product (and bias-gradient partial) into slab y; the slabs are then added in
-            // ascending order: bit-reproducible, no float atomics (the atomic form drifts after a few Adam steps)
-            float* slab = reinterpret_cast<float*>(WS(p, p->o_cslab));
-            const int64_t wn = (int64_t)L.kdim * L.cout_np;
-            e.kind = DMVAE_EPI_STORE_F32; e.out = slab; e.out2 = slab + (int64_t)sp * wn;
-            GemmArgs g;
-            TRY(gemm_checked(s, dt, DMVAE_GEMM_DW, L.kdim, L.cout_np, M, in, L.cin_ld, dact, L.cout_ld, &e, 1, &g, L.P, L.cin));
-            g.k_split = M / sp; g.slab_stride = wn; g.slab_stride2 = L.cout_np;
-            if (dt == DMVAE_BF16) TRY(gemm_bf16_dispatch(s, DMVAE_GEMM_DW, g, sp));
-            else {
-                ProfScope ps(s, "gemm_f32_dw", 2.0 * g.M * g.N * (double)g.K, 4.0 * ((double)g.M * g.K + (double)g.K * g.N + (double)g.M * g.N));
-                TRY(gemm_f32_dispatch(s, DMVAE_GEMM_DW, g, sp));
-            }
-            TRY(slab_reduce_launch(s, slab, wn, sp, wn, p->buf.grad + L.w_off));
-            TRY(slab_reduce_launch(s, slab + (int64_t)sp * wn, L.cout_np, sp, L.cout_np, p->buf.grad + L.b_off));
-        } else
-        TRY(gemm_checked(s, dt, DMVAE_GEMM_DW, L.kdim, L.cout_np, M, in, L.cin_ld, dact, L.cout_ld, &e, sp, nullptr, L.P, L.cin));
-        if (L.kdim > 9 * L.cin) {   // rows past the ninth tap are padding: the GEMM filled them with a copy of tap 8
-            me = hipMemsetAsync(p->buf.grad + L.w_off + (int64_t)9 * L.cin * L.cout_np, 0, (size_t)(L.kdim - 9 * L.cin) * L.cout_np * 4, s);
-            if (me != hipSuccess) { set_error("conv gradient pad memset: %s", hipGetErrorString(me)); return (int)me; }
-        }
+        TRY(conv_layer_dw(s, dt, M, L.P, L.cin, L.kdim, in, L.cin_ld, dact, L.cout_ld, L.cout_np, L.cout,
+                          conv_dw_split(M, (L.kdim / 64) * (L.cout_np / 64)), reinterpret_cast<float*>(WS(p, p->o_cslab)), p->buf.grad + L.w_off, p->buf.grad + L.b_off));
         TRY(conv_wflip_launch(s, dt, Wp(p, L.w_off), L.cin, L.cin_np, L.cout, L.cout_np, WS(p, p->o_wt), L.ktdim));
+        dmvae_epilogue e;
         memset(&e, 0, sizeof(e));
         e.kind = DMVAE_EPI_RELU_MASK; e.ldo = L.cin_ld; e.aux0 = in; e.ld0 = L.cin_ld; e.n_valid = L.cin;
         e.out = Lp.pool ? rows0(p, Lp.o_dpool, L.P, L.cin_ld) : rows0(p, Lp.o_dact, L.P, L.cin_ld);
@@ -1581,6 +1590,54 @@ extern "C" int dmvae_debug_anatomy256(void** device_ptr) {
     if (!device_ptr) return DMVAE_EINVAL;
     *device_ptr = gemm_bf16_256_anatomy();
     return *device_ptr ? 0 : DMVAE_ESTATE;
+}
+
+// ---- the CNN trunk's kernels on caller-owned buffers (tests/test_gpu_conv_kernels.py): thin wrappers over the launchers of conv.hip
+extern "C" int dmvae_debug_conv_first_fwd(void* stream, int dtype, const void* x, int64_t bstride, int H, int64_t n_img, const void* W, int ldw,
+                                          const float* bias, void* out, int ld) {
+    DMVAE_REQUIRE((dtype == DMVAE_F32 || dtype == DMVAE_BF16) && x && W && bias && out && H > 0 && n_img > 0 && bstride >= (int64_t)H * H, "dmvae_debug_conv_first_fwd: bad argument");
+    return conv_first_fwd_launch((hipStream_t)stream, dtype, x, bstride, H, n_img, W, ldw, bias, 32, out, ld);
+}
+extern "C" int dmvae_debug_conv_first_dw(void* stream, int dtype, const void* x, int64_t bstride, int H, int64_t n_img, const void* dY, int ld,
+                                         float* dW, int ldw, float* db, float* part, int64_t part_floats, int* n_blocks) {
+    DMVAE_REQUIRE((dtype == DMVAE_F32 || dtype == DMVAE_BF16) && H > 0 && H % 4 == 0 && n_img > 0 && (ld == 32 || ld == 64) && n_blocks &&
+                  n_img * H * (H / 4) < (1ll << 31), "dmvae_debug_conv_first_dw: bad argument (side a multiple of 4, ld 32 or 64)");      // what the launcher takes: the size query answers for nothing else
+    *n_blocks = conv_first_dw_blocks(H, n_img);
+    if (!part) return 0;                       // size query
+    DMVAE_REQUIRE(x && dY && dW && db && bstride >= (int64_t)H * H && part_floats >= (int64_t)*n_blocks * 320,
+                  "dmvae_debug_conv_first_dw: bad argument (scratch: %d blocks x 320 floats)", *n_blocks);
+    return conv_first_dw_launch((hipStream_t)stream, dtype, x, bstride, H, n_img, dY, ld, 32, dW, ldw, db, part);
+}
+extern "C" int dmvae_debug_zero_border(void* stream, int dtype, void* a, int P, int ld, int64_t n_img) {
+    DMVAE_REQUIRE((dtype == DMVAE_F32 || dtype == DMVAE_BF16) && a && P >= 2 && n_img > 0, "dmvae_debug_zero_border: bad argument");
+    return zero_border_launch((hipStream_t)stream, dtype, a, P, ld, n_img);
+}
+extern "C" int dmvae_debug_maxpool2_fwd(void* stream, int dtype, const void* in, int H, int ld, int64_t n_img, void* out, int out_border) {
+    DMVAE_REQUIRE((dtype == DMVAE_F32 || dtype == DMVAE_BF16) && in && out && H > 0 && n_img > 0 && (out_border == 0 || out_border == 1), "dmvae_debug_maxpool2_fwd: bad argument");
+    return maxpool2_fwd_launch((hipStream_t)stream, dtype, in, H, ld, n_img, out, out_border);
+}
+extern "C" int dmvae_debug_maxpool2_bwd_relu(void* stream, int dtype, const void* in, const void* dout, int H, int ld, int64_t n_img, void* din, int dout_border) {
+    DMVAE_REQUIRE((dtype == DMVAE_F32 || dtype == DMVAE_BF16) && in && dout && din && H > 0 && n_img > 0 && (dout_border == 0 || dout_border == 1), "dmvae_debug_maxpool2_bwd_relu: bad argument");
+    return maxpool2_bwd_relu_launch((hipStream_t)stream, dtype, in, dout, H, ld, n_img, din, dout_border);
+}
+extern "C" int dmvae_debug_conv_wflip(void* stream, int dtype, const void* W, int cin, int cin_ld, int cout, int ldw, void* Wt, int Kt) {
+    DMVAE_REQUIRE((dtype == DMVAE_F32 || dtype == DMVAE_BF16) && W && Wt && cin > 0 && cout > 0 && ldw >= cout, "dmvae_debug_conv_wflip: bad argument");
+    return conv_wflip_launch((hipStream_t)stream, dtype, W, cin, cin_ld, cout, ldw, Wt, Kt);
+}
+extern "C" int dmvae_debug_conv_gemm(void* stream, int dtype, int layout, int M, int N, int K, const void* A, int64_t lda,
+                                     const void* B, int64_t ldb, const dmvae_epilogue* epi, int split_k, int conv_p, int conv_c) {
+    DMVAE_REQUIRE(conv_p >= 3 && conv_c > 0, "dmvae_debug_conv_gemm: conv_p = side + 2 >= 3, conv_c > 0");
+    return gemm_checked((hipStream_t)stream, dtype, layout, M, N, K, A, lda, B, ldb, epi, split_k, nullptr, conv_p, conv_c);
+}
+extern "C" int dmvae_debug_conv_dw(void* stream, int dtype, int rows, int conv_p, int conv_c, const void* X, int64_t ldx, const void* dY, int64_t ldy,
+                                   int N, int n_valid, int split, float* slab, float* dW, float* db) {
+    DMVAE_REQUIRE(rows > 0 && conv_p >= 3 && conv_c > 0 && N > 0 && n_valid > 0 && n_valid <= N && dW && db && split >= 1 && rows % (split * 64) == 0 && (split == 1 || slab),
+                  "dmvae_debug_conv_dw: bad argument");
+    const int kdim = pad64(9 * conv_c);
+    hipError_t me = hipMemsetAsync(dW, 0, (size_t)kdim * N * 4, (hipStream_t)stream);      // (the plan zeroes its whole conv gradient range up front)
+    if (me == hipSuccess) me = hipMemsetAsync(db, 0, (size_t)N * 4, (hipStream_t)stream);
+    if (me != hipSuccess) { set_error("dmvae_debug_conv_dw memset: %s", hipGetErrorString(me)); return (int)me; }
+    return conv_layer_dw((hipStream_t)stream, dtype, rows, conv_p, conv_c, kdim, X, ldx, dY, ldy, N, n_valid, split, slab, dW, db);
 }
 
 extern "C" int dmvae_prof_enable(int on) {

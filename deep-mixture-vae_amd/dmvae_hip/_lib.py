@@ -42,6 +42,8 @@ EXPORTS = [
     "dmvae_gmm_seed_ws_bytes", "dmvae_gmm_seed", "dmvae_philox_uniform",
     "dmvae_confusion_add", "dmvae_plan_eval_clusters",
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
+    "dmvae_debug_conv_first_fwd", "dmvae_debug_conv_first_dw", "dmvae_debug_zero_border", "dmvae_debug_maxpool2_fwd", "dmvae_debug_maxpool2_bwd_relu",
+    "dmvae_debug_conv_wflip", "dmvae_debug_conv_gemm", "dmvae_debug_conv_dw",
 ]
 
 
@@ -242,6 +244,14 @@ def _load():
         "dmvae_prof_collect": [P(ProfRow), i32],
         "dmvae_debug_set_tile": [i32, i32],
         "dmvae_debug_set_knob": [i32, i32],
+        "dmvae_debug_conv_first_fwd": [vp, i32, vp, i64, i32, i64, vp, i32, vp, vp, i32],
+        "dmvae_debug_conv_first_dw": [vp, i32, vp, i64, i32, i64, vp, i32, vp, i32, vp, vp, i64, P(C.c_int)],
+        "dmvae_debug_zero_border": [vp, i32, vp, i32, i32, i64],
+        "dmvae_debug_maxpool2_fwd": [vp, i32, vp, i32, i32, i64, vp, i32],
+        "dmvae_debug_maxpool2_bwd_relu": [vp, i32, vp, vp, i32, i32, i64, vp, i32],
+        "dmvae_debug_conv_wflip": [vp, i32, vp, i32, i32, i32, i32, vp, i32],
+        "dmvae_debug_conv_gemm": [vp, i32, i32, i32, i32, i32, vp, i64, vp, i64, P(Epilogue), i32, i32, i32],
+        "dmvae_debug_conv_dw": [vp, i32, i32, i32, i32, vp, i64, vp, i64, i32, i32, i32, vp, vp, vp],
         "dmvae_abi_version": [],
         "dmvae_last_error": [],
     }

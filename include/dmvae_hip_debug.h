@@ -2,7 +2,8 @@
  * dmvae_hip_debug.h -- measurement and tuning entry points of libdmvae_hip.so.
  *
  * NOT part of the drop-in boundary (include/dmvae_hip.h): nothing here replaces a line of the reference.
- * bench.py's roofline leg uses dmvae_prof_* / dmvae_debug_spin; tools/ uses the probes and knobs.
+ * bench.py's roofline leg uses dmvae_prof_* / dmvae_debug_spin; tools/ uses the probes and knobs; tests/test_gpu_conv_kernels.py
+ * runs every kernel of the CNN trunk alone, on buffers of its own, through dmvae_debug_conv_* / _zero_border / _maxpool2_*.
  */
 #ifndef DMVAE_HIP_DEBUG_H
 #define DMVAE_HIP_DEBUG_H
@@ -93,6 +94,33 @@ int dmvae_debug_set_tile(int bm, int bn);
  *                       heads + latent launch while blocks x slices <= 256), joined by the last workgroup to arrive (GemmArgs::tick): 1 (default) slices of
  *                       512, 2 slices of 256 (0.1397 vs 0.1402 ms at 100 rows: the same), 0 none */
 int dmvae_debug_set_knob(int which, int value);
+
+/* ---- the CNN trunk's kernels on caller-owned buffers (csrc/conv.hip; tests/test_gpu_conv_kernels.py) ----------
+ * dtype = DMVAE_F32 | DMVAE_BF16 is the activation AND weight type.  A zero-bordered activation is [n_img][P][P][ld], P = side + 2,
+ * and pointers to one address padded pixel 0; the conv-mode GEMMs read up to P + 1 rows in front of it and behind its end.
+ * first layer: x = [n_img][bstride] images of H x H pixels (H % 4 == 0), W = [9][ldw] with 32 outputs, out / dY = [n_img][H+2][H+2][ld], ld = 32 | 64;
+ * the forward writes interior pixels only. */
+int dmvae_debug_conv_first_fwd(void* stream, int dtype, const void* x, int64_t bstride, int H, int64_t n_img, const void* W, int ldw,
+                               const float* bias, void* out, int ld);
+/* dW = [9][ldw], db = [32]; *n_blocks = the partial-sum blocks of this geometry; part = n_blocks x 320 floats of scratch (part == NULL: only the count) */
+int dmvae_debug_conv_first_dw(void* stream, int dtype, const void* x, int64_t bstride, int H, int64_t n_img, const void* dY, int ld,
+                              float* dW, int ldw, float* db, float* part, int64_t part_floats, int* n_blocks);
+int dmvae_debug_zero_border(void* stream, int dtype, void* a, int P, int ld, int64_t n_img);
+/* SAME 2x2 / stride-2 max-pool of a zero-bordered [n_img][H+2][H+2][ld]; out is zero-bordered (out_border = 1: interior written only) or plain */
+int dmvae_debug_maxpool2_fwd(void* stream, int dtype, const void* in, int H, int ld, int64_t n_img, void* out, int out_border);
+/* its gradient behind a ReLU: first maximum of the window in row-major order, gated by in > 0; writes the interior pixels of din */
+int dmvae_debug_maxpool2_bwd_relu(void* stream, int dtype, const void* in, const void* dout, int H, int ld, int64_t n_img, void* din, int dout_border);
+/* W = [9 * cin][ldw] -> Wt = [cin_ld][Kt], column (tap, co) = W[(8 - tap, ci)][co]; zero pad rows / columns */
+int dmvae_debug_conv_wflip(void* stream, int dtype, const void* W, int cin, int cin_ld, int cout, int ldw, void* Wt, int Kt);
+/* dmvae_gemm in conv mode (implicit 3x3 SAME convolution over padded pixel rows): conv_p = P, conv_c = channels per tap of the A operand;
+ * FWD + BIAS_RELU, DX + RELU_MASK, DW + ATOMIC_F32 / STORE_F32; epi->n_valid = the real output columns */
+int dmvae_debug_conv_gemm(void* stream, int dtype, int layout, int M, int N, int K, const void* A, int64_t lda,
+                          const void* B, int64_t ldb, const dmvae_epilogue* epi, int split_k, int conv_p, int conv_c);
+/* weight + bias gradient of one convolution layer exactly as the plan's backward pass runs it, for a given K split over `rows` padded pixel rows:
+ * dW = [pad64(9 * conv_c)][N], db = [N] (both zeroed first); split 1: fp32 atomics; split > 1: K-slice slabs in `slab`
+ * (split * (pad64(9 * conv_c) + 1) * N floats) added in a fixed order; the pad rows past the ninth tap are zeroed */
+int dmvae_debug_conv_dw(void* stream, int dtype, int rows, int conv_p, int conv_c, const void* X, int64_t ldx, const void* dY, int64_t ldy,
+                        int N, int n_valid, int split, float* slab, float* dW, float* db);
 
 #ifdef __cplusplus
 }
