@@ -421,7 +421,9 @@ extern "C" int dmvae_plan_create(const dmvae_config* c, dmvae_plan** out) {
     // (latent_blocks_now) and checked against this capacity.
     p->n_lblk_cap = std::max(p->n_lblk, (p->Bp + 15) / 16);
     p->o_lpart = take((int64_t)p->n_lblk_cap * 2 * 4);
-    p->lws_bytes = (!p->vade && latent_mfma_applies(c->latent_dim, c->n_classes, c->mode)) ? latent_mfma_ws_bytes(p->Bp, c->latent_dim, c->n_classes) : 0;
+    // (VaDE: tables past the one-kernel form's LDS take latent_vade_mfma.hip -- the step and dmvae_plan_eval_clusters share this scratch)
+    p->lws_bytes = p->vade ? (latent_vade_mfma_needed(c->latent_dim, c->n_classes) ? latent_vade_mfma_ws_bytes(p->Bp, c->latent_dim, c->n_classes, nullptr) : 0)
+                 : latent_mfma_applies(c->latent_dim, c->n_classes, c->mode) ? latent_mfma_ws_bytes(p->Bp, c->latent_dim, c->n_classes) : 0;
     p->n_pblk = p->lws_bytes ? 1 : p->n_lblk;          // the MFMA form delivers the prior-table gradient complete, in one row
     p->o_dprior = take((int64_t)(p->lws_bytes ? 1 : p->n_lblk_cap) * 2 * KD * 4);
     if (p->lws_bytes) p->o_lws = take(p->lws_bytes);
@@ -898,6 +900,7 @@ extern "C" int dmvae_plan_eval_clusters(dmvae_plan* p, void* stream, int n_valid
     a.eps = eps; a.ld_eps = ld_eps;
     a.seed = c.seed; a.counter = eval_counter;
     a.w = reinterpret_cast<float*>(WS(p, p->o_lg)); a.ld_w = p->Kp;
+    a.B_pad = p->Bp; a.ws = p->lws_bytes ? reinterpret_cast<float*>(WS(p, p->o_lws)) : nullptr; a.ws_bytes = p->lws_bytes;
     TRY(vade_eval_check(a, "dmvae_plan_eval_clusters"));
     TRY(encode_impl(p, s));
     return vade_eval_launch(s, a);
@@ -1467,7 +1470,13 @@ extern "C" int dmvae_gemm_grouped_dw_adam(void* stream, const dmvae_gemm_problem
 extern "C" int dmvae_latent_nblocks(int B_pad, int D, int K) { return latent_nblocks(B_pad, D, K); }
 extern "C" int dmvae_latent_nblocks_vade(int B_pad) { return latent_vade_nblocks(B_pad); }
 extern "C" int64_t dmvae_latent_ws_bytes(int B_pad, int D, int K, int mode) {
+    if (mode == 2) return dmvae_latent_vade_ws_bytes(B_pad, D, K, 0, nullptr);
     return (B_pad > 0 && B_pad % 64 == 0 && latent_mfma_applies(D, K, mode)) ? latent_mfma_ws_bytes(B_pad, D, K) : 0;
+}
+extern "C" int64_t dmvae_latent_vade_ws_bytes(int B_pad, int D, int K, int forced, int* n_slabs) {
+    if (n_slabs) *n_slabs = 0;
+    if (B_pad <= 0 || B_pad % 64 != 0 || D < 1 || K < 1 || (!forced && !latent_vade_mfma_needed(D, K))) return 0;
+    return latent_vade_mfma_ws_bytes(B_pad, D, K, n_slabs);
 }
 extern "C" int dmvae_latent_fwd(void* stream, const dmvae_latent_args* a) {
     DMVAE_REQUIRE(a && a->mode >= 0 && a->mode <= 2, "dmvae_latent_fwd: bad mode %d", a ? a->mode : -1);
@@ -1707,8 +1716,9 @@ extern "C" int dmvae_debug_set_knob(int which, int value) {
     if (which == 18 || which == 20) { gemm_bf16_set_knob(which, value); return 0; }
     if (which == 19) { heads_latent_set(value); return 0; }
     if (which == 21) { g_ksplit = value; return 0; }
+    if (which == 22) { latent_vade_force_mfma(value); return 0; }
     if (which == 14) { latent_set_blocks_target(value); return 0; }      // (the block count in use is taken at enqueue time and checked against the plan's capacity)
-    DMVAE_REQUIRE(which >= 0 && which <= 9 && which != 3, "dmvae_debug_set_knob: knob 0 = supertile rows, 1 = 8-wave workgroups, 2 = per-problem tiles in grouped grids, (3: removed, the deep-ring policy), 4 = XCD runs per tile class in grouped grids, 5 = short-K conv tiles, 6 = 256x256 tile policy, 7 = short-K workgroups, 8 = first-tile stagger of the merged dW grid, 9 = waves per workgroup of a grouped dX launch; 10 / 11 = K slices of the dW groups, 12 = heads dX as one or two launches, 13 = heads dX on the streaming kernel (1) or the grouped tiles (0), 14 = blocks the latent kernel's geometry aims at (512), 19 = fused heads + latent launch, 20 = XCD partition of the grouped dW launch, 21 = K slices of a small batch's thin launches");
+    DMVAE_REQUIRE(which >= 0 && which <= 9 && which != 3, "dmvae_debug_set_knob: knob 0 = supertile rows, 1 = 8-wave workgroups, 2 = per-problem tiles in grouped grids, (3: removed, the deep-ring policy), 4 = XCD runs per tile class in grouped grids, 5 = short-K conv tiles, 6 = 256x256 tile policy, 7 = short-K workgroups, 8 = first-tile stagger of the merged dW grid, 9 = waves per workgroup of a grouped dX launch; 10 / 11 = K slices of the dW groups, 12 = heads dX as one or two launches, 13 = heads dX on the streaming kernel (1) or the grouped tiles (0), 14 = blocks the latent kernel's geometry aims at (512), 19 = fused heads + latent launch, 20 = XCD partition of the grouped dW launch, 21 = K slices of a small batch's thin launches, 22 = VaDE's large-table latent form wherever the caller brings its scratch");
     gemm_bf16_set_knob(which, value);
     return 0;
 }

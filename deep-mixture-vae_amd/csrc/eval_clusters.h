@@ -27,6 +27,9 @@ struct VadeEvalArgs {
     const float* eps; int64_t ld_eps;                           // [draws][n_valid][ld_eps] or nullptr: Philox
     uint64_t seed, counter;
     float* w; int64_t ld_w;                                     // [n_valid][>= K] averaged responsibilities
+    // tables past the LDS limit of vade_eval_kernel (latent_vade_mfma_needed): the scratch of the large-table form for B_pad rows
+    // (latent_vade_mfma_ws_bytes), B_pad % 64 == 0 and >= n_valid; not read otherwise
+    int B_pad; float* ws; int64_t ws_bytes;
 };
 
 // 0, or DMVAE_EINVAL / DMVAE_EUNSUPPORTED with the error text set (nothing is enqueued)
@@ -34,5 +37,6 @@ int eval_rows_check(const EvalRows& r, int K, const char* who);
 int vade_eval_check(const VadeEvalArgs& a, const char* who);
 int confusion_add_launch(hipStream_t s, const float* scores, int64_t ld, int K, const EvalRows& r);
 int vade_eval_launch(hipStream_t s, const VadeEvalArgs& a);
+int vade_eval_mfma_launch(hipStream_t s, const VadeEvalArgs& a);      // latent_vade_mfma.hip; through vade_eval_launch only
 
 }  // namespace dmvae

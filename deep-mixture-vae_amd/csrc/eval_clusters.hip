@@ -9,7 +9,9 @@
 //                          ascending order  Z_j = mean + exp(log_var / 2) eps_j,  gamma_j = get_cluster_probs(Z_j)
 //                          (priors.py:91-102; the formula is in the header of latent_vade.hip),  w = (sum_j gamma_j) / k,
 //                          written out, then the same arg-max and count on w.  The prior tables are whole in LDS as
-//                          latent_vade_kernel holds them.  eps_j: the caller's buffer [k][n][ld_eps], or Philox keyed by
+//                          latent_vade_kernel holds them; tables past its 60 KiB take the per-draw forward half of
+//                          latent_vade_mfma.hip (vade_eval_mfma_launch), then confusion_add_kernel on w.
+//                          eps_j: the caller's buffer [k][n][ld_eps], or Philox keyed by
 //                          (seed, counter, stream EVAL_PHILOX_STREAM, element ((j * n_rows + first + r) * D + d)): the
 //                          noise of a row depends on its POSITION in the evaluated order, not on the batch size.
 //
@@ -158,11 +160,6 @@ __global__ __launch_bounds__(256) void vade_eval_kernel(VadeEvalArgs a) {
 static size_t vade_eval_lds_bytes(int D, int K) {
     return sizeof(float) * ((size_t)2 * K * (D + 1) + K + (size_t)2 * EVAL_RB * K + (size_t)3 * EVAL_RB * (D + 1));
 }
-// what latent_vade_kernel asks for (latent_vade.hip): the limit of the step is the limit of the evaluation
-static size_t vade_step_lds_bytes(int D, int K) {
-    return sizeof(float) * ((size_t)2 * K * (D + 1) + K + (size_t)2 * 16 * K + (size_t)4 * 16 * (D + 1) + 32);
-}
-
 #define EVAL_REQUIRE(cond, ...) do { if (!(cond)) { set_error(__VA_ARGS__); return DMVAE_EINVAL; } } while (0)
 
 int eval_rows_check(const EvalRows& r, int K, const char* who) {
@@ -179,10 +176,11 @@ int vade_eval_check(const VadeEvalArgs& a, const char* who) {
     EVAL_REQUIRE(a.D >= 1 && a.mean && a.log_var && a.prior_means && a.prior_log_vars && a.w, "%s: null pointer / D=%d", who, a.D);
     EVAL_REQUIRE(a.draws >= 1 && a.draws <= EVAL_MAX_DRAWS, "%s: draws=%d (1 .. %d)", who, a.draws, EVAL_MAX_DRAWS);
     EVAL_REQUIRE(a.ld_mean >= a.D && a.ld_log_var >= a.D && a.ld_w >= a.K && (!a.eps || a.ld_eps >= a.D), "%s: leading dimension too small", who);
-    const size_t lb = vade_step_lds_bytes(a.D, a.K);
-    if (lb > 60 * 1024) {
-        set_error("%s (VaDE): K=%d D=%d needs %zu B of LDS: the VaDE latent stage keeps its prior tables whole in LDS", who, a.K, a.D, lb);
-        return DMVAE_EUNSUPPORTED;
+    if (latent_vade_mfma_needed(a.D, a.K)) {          // the limit of the step's one-kernel form is the limit of vade_eval_kernel
+        const int64_t need = a.B_pad > 0 && a.B_pad % 64 == 0 ? latent_vade_mfma_ws_bytes(a.B_pad, a.D, a.K, nullptr) : 0;
+        EVAL_REQUIRE(need > 0 && a.B_pad >= a.rows.n_valid && a.ws && a.ws_bytes >= need,
+                     "%s (VaDE): K=%d D=%d takes the large-table form, which needs %lld bytes of scratch for B_pad=%d rows (a multiple of 64, >= n_valid=%d)",
+                     who, a.K, a.D, (long long)need, a.B_pad, a.rows.n_valid);
     }
     return 0;
 }
@@ -200,6 +198,7 @@ int confusion_add_launch(hipStream_t s, const float* scores, int64_t ld, int K, 
 int vade_eval_launch(hipStream_t s, const VadeEvalArgs& a) {
     if (int rc = vade_eval_check(a, "dmvae_plan_eval_clusters")) return rc;
     if (a.rows.n_valid == 0) return 0;
+    if (latent_vade_mfma_needed(a.D, a.K)) return vade_eval_mfma_launch(s, a);
     const int nblk = (a.rows.n_valid + EVAL_RB - 1) / EVAL_RB;
     const double n = a.rows.n_valid;
     ProfScope ps(s, "vade_eval", 3.0 * n * a.draws * (double)a.K * a.D,

@@ -43,7 +43,8 @@ void heads_dx_stream_set(int v);
 void gemm_bf16_force_tile(int t);
 void gemm_bf16_set_knob(int which, int v);
 int gemm_f32_dispatch(hipStream_t s, int layout, const GemmArgs& a, int split);
-// three STORE_F32 problems (forward / dX / dW layout, in that order) with split1 / split2 / split3 K slices as ONE grid (latent_mfma.hip)
+// three STORE_F32 problems (forward / dX / dW layout, in that order) with split1 / split2 / split3 K slices as ONE grid (latent_mfma.hip);
+// a problem with M = 0 is absent (latent_vade_mfma.hip: forward + dW)
 int gemm_f32_trio(hipStream_t s, const GemmArgs& g1, int split1, const GemmArgs& g2, int split2, const GemmArgs& g3, int split3);
 int latent_nblocks(int B_pad, int D, int K);
 int latent_launch(hipStream_t s, const dmvae_latent_args* a);
@@ -51,6 +52,13 @@ void latent_set_blocks_target(int v);
 // VaDE's latent stage (latent_vade.hip): mode 2
 int latent_vade_nblocks(int B_pad);
 int latent_vade_launch(hipStream_t s, const dmvae_latent_args* a);
+size_t latent_vade_lds_bytes(int D, int K);              // LDS need of the one-kernel form; above 60 KiB:
+// the large-table form (latent_vade_mfma.hip): the contractions as exact-f32 MFMA GEMMs, scratch in dmvae_latent_args.mfma_ws
+bool latent_vade_mfma_needed(int D, int K);
+bool latent_vade_mfma_forced();                          // debug knob 22
+void latent_vade_force_mfma(int v);
+int64_t latent_vade_mfma_ws_bytes(int B_pad, int D, int K, int* n_slabs);      // n_slabs: batch slabs of the two table contractions together
+int latent_vade_mfma_launch(hipStream_t s, const dmvae_latent_args* a, float* ws, int64_t ws_bytes);
 // the two head layers' forward pass + the latent stage as one launch (heads_latent.hip); rows_per_latent_block: what latent_nblocks implies (must be 16)
 bool heads_latent_ok(int B_pad, int D, int K, int Dp, int Kp, int Hp, int mode, int rows_per_latent_block);
 int heads_latent_launch(hipStream_t s, const dmvae_latent_args* a, const dmvae_heads_args* h);

@@ -19,15 +19,11 @@
 // The [B, K, D] tensor TensorFlow materialises is still never formed; the intermediates are [B, 2D] and [B, K].
 // No float atomics: G3's split over the batch writes slabs.  Device noise: one Philox block per four columns of a
 // row, keyed by the element index (a different, equally valid stream than latent.hip's geometry-keyed one).
-#include <string.h>
-
 #include <algorithm>
 
-#include "kernels.h"
+#include "latent_tables.h"
 
 namespace dmvae {
-
-static inline int pad64i(int x) { return (x + 63) / 64 * 64; }
 
 struct LatentMfmaWs {      // float offsets into the caller's scratch
     int Dp, Kp, XW, nsplit, nsplit_s;      // K slices of G3 (over the batch) and of G2 (over 2D)
@@ -57,30 +53,6 @@ static LatentMfmaWs latent_mfma_layout(int Bp, int D, int K) {
 
 bool latent_mfma_applies(int D, int K, int mode) { return mode == 0 && (int64_t)D * K >= 4096; }
 int64_t latent_mfma_ws_bytes(int B_pad, int D, int K) { return 4 * latent_mfma_layout(B_pad, D, K).total; }
-
-// ---- prior tables -> GEMM operands (tiny: K * D elements)
-__device__ __forceinline__ void latent_tables_block(const int k, const float* __restrict__ pm, const float* __restrict__ plv, int K, int D, int Kp, int Dp,
-                                                    float* __restrict__ T1, float* __restrict__ T2, float* __restrict__ c2, float* __restrict__ ck, float* red) {
-    // one block per (padded) cluster row k
-    float s2 = 0.f, sl = 0.f;
-    for (int d = threadIdx.x; d < Dp; d += 256) {
-        float ip = 0.f, m = 0.f;
-        if (k < K && d < D) {
-            const float lv = plv[(int64_t)k * D + d];
-            m = pm[(int64_t)k * D + d];
-            ip = __expf(-lv);
-            s2 += m * m * ip;
-            sl += lv;
-        }
-        T1[(int64_t)k * 2 * Dp + d] = ip;
-        T1[(int64_t)k * 2 * Dp + Dp + d] = m * ip;
-        T2[(int64_t)k * 2 * Dp + d] = ip;
-        T2[(int64_t)k * 2 * Dp + Dp + d] = -2.f * m * ip;
-    }
-    const float a = block_sum_256(s2, red);
-    const float b = block_sum_256(sl, red + 4);
-    if (threadIdx.x == 0) { c2[k] = a; ck[k] = b; }
-}
 
 struct LatentMfmaArgs {
     dmvae_latent_args a;
@@ -494,16 +466,6 @@ __global__ __launch_bounds__(256) void latent_post_kernel(LatentMfmaArgs L, int 
         for (int i = 0; i < 16; ++i) z += red[i];
         a.loss_partials[2 * blockIdx.x] = z;
     }
-}
-
-static GemmArgs f32_problem(int M, int N, int K, const float* A, int64_t lda, const float* B, int64_t ldb, float* out, int64_t ldo,
-                            int split, int64_t slab_stride) {
-    GemmArgs g;
-    g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = M; g.N = N; g.K = K; g.k_split = K / split; g.group_m = 8; g.conv_p = 0; g.conv_c = 0;
-    memset(&g.epi, 0, sizeof(g.epi));
-    g.epi.kind = DMVAE_EPI_STORE_F32; g.epi.out = out; g.epi.ldo = ldo; g.epi.m_valid = M; g.epi.n_valid = N;
-    g.slab_stride = slab_stride;
-    return g;
 }
 
 int latent_mfma_launch(hipStream_t s, const dmvae_latent_args* a, float* ws, int64_t ws_bytes) {

@@ -11,8 +11,12 @@
 //     gmu' = dKL/dmean|gamma + dZ_lat,     glv' = dKL/dlog_var|gamma + dZ_lat * clv        (clv = eps/2 exp(lv/2))
 // and the backward of the stage is again  dmean = dZ + gmu',  dlog_var = dZ * clv + glv'.
 // Geometry: 16 lanes per row, 16 rows per 256-thread workgroup, the prior tables whole in LDS (VaDE's tables are
-// small: 10 x 10 in the reference); larger tables than ~50 KiB return DMVAE_EUNSUPPORTED.  Per-block partials of the
-// prior-table gradients, summed in a fixed order by step_finalize (no float atomics).
+// small: 10 x 10 in the reference).  Per-block partials of the prior-table gradients, summed in a fixed order by
+// step_finalize (no float atomics).
+// Dispatch (latent_vade_launch): this kernel while its LDS need, 4 (2 K (D + 1) + 33 K + 64 (D + 1) + 32) bytes, is at most
+// 60 KiB (D = 128 with K = 10 still fits; D = 256 does not for any K); every larger table takes the tiled MFMA form of
+// latent_vade_mfma.hip, which needs the caller's scratch (dmvae_latent_args.mfma_ws, dmvae_latent_vade_ws_bytes()).  Debug
+// knob 22 sends every shape that fits here to that form too; a caller without the scratch then gets DMVAE_EINVAL.
 #include "kernels.h"
 
 namespace dmvae {
@@ -179,7 +183,7 @@ __global__ __launch_bounds__(256) void latent_vade_kernel(dmvae_latent_args a) {
     }
 }
 
-static size_t vade_lds_bytes(int D, int K) {
+size_t latent_vade_lds_bytes(int D, int K) {
     return sizeof(float) * ((size_t)2 * K * (D + 1) + K + (size_t)2 * 16 * K + (size_t)4 * 16 * (D + 1) + 32);
 }
 int latent_vade_nblocks(int B_pad) { return B_pad / 16; }
@@ -189,11 +193,10 @@ int latent_vade_launch(hipStream_t s, const dmvae_latent_args* a) {
         set_error("dmvae_latent_fwd (VaDE): B_pad=%d must be a multiple of 64 and >= B=%d", a->B_pad, a->B);
         return DMVAE_EINVAL;
     }
-    const size_t lb = vade_lds_bytes(a->D, a->K);
-    if (lb > 60 * 1024) {
-        set_error("dmvae_latent_fwd (VaDE): K=%d D=%d needs %zu B of LDS: the VaDE latent stage keeps its prior tables whole in LDS", a->K, a->D, lb);
-        return DMVAE_EUNSUPPORTED;
-    }
+    const size_t lb = latent_vade_lds_bytes(a->D, a->K);
+    // (the knob forces: a caller without the scratch gets the large-table form's DMVAE_EINVAL, never the other kernel without a word)
+    if (lb > 60 * 1024 || latent_vade_mfma_forced())
+        return latent_vade_mfma_launch(s, a, reinterpret_cast<float*>(a->mfma_ws), a->mfma_ws_bytes);
     const int nblk = a->B_pad / 16;
     ProfScope ps(s, "latent_vade", 14.0 * a->B * (double)a->K * a->D, 4.0 * ((double)a->B * (7.0 * a->D + a->K) + 2.0 * a->K * a->D * (nblk + 1)));
     DMVAE_LAUNCH(latent_vade_kernel, dim3(nblk), dim3(256), lb, s, *a);

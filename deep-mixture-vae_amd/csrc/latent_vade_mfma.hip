@@ -1,0 +1,575 @@
+// Large-table form of VaDE's latent stage (mode 2; the one-kernel form and the formulas of the stage: latent_vade.hip, which
+// keeps both prior tables whole in LDS and so stops at 60 KiB).  The (row, cluster, dimension) contractions as exact-f32 MFMA
+// GEMMs (v_mfma_f32_16x16x4_f32 through gemm_f32.hip, as latent_mfma.hip does for DMVAE), taken twice -- once for the mean,
+// once for the sample.  With ip = exp(-plv), pm = prior mean, e = exp(lv), mu = mean, z = mu + exp(lv / 2) eps,
+// cl = eps / 2 exp(lv / 2), r = kl_ratio, c2_k = sum_d pm^2 ip, ck_k = sum_d plv, over 2 B STACKED rows (mean rows, then
+// sample rows):
+//
+//   X   = [e + mu^2 | mu | 1] ; [z^2 | z | 1]                                        [2B][2D + 64]   (vade_pre)
+//   S   = X . [ip | -2 pm ip]^T          S_mu + c2 + ck - sum_d lv - D = T,   u = -1/2 (S_z + c2 + ck)            (G2)
+//   gamma = softmax_k(u),  G = r/B (T/2 + log(gamma + e0) + gamma / (gamma + e0) + log K),  du = gamma (G - sum gamma G)
+//   (G taken relative to the row's smallest T / 2, without log K: the same du, see vade_rows),
+//   KL_Z, KL_C                                                                       W2 = gamma ; du  [2B][K] (vade_rows)
+//   [A | C] ; [A_u | C_u] = W2 . [ip | pm ip]                                                                     (G1)
+//         -> dZ_lat = -(z A_u - C_u),  gmu = r/B (mu A - C) + dZ_lat,  glv = r/2B (e A - 1) + dZ_lat cl    (vade_post)
+//   G_gamma = gamma^T . [e + mu^2 | mu | 1],  G_u = du^T . [z^2 | z | 1]     ONE problem contracted over the 2B stacked rows
+//         whose K slices never straddle row B: the first half of its slabs sums to G_gamma, the second to G_u    (G3)
+//         -> d pm  = -r/B ip (Gg_mu - pm Wsum) + ip (Gu_z - pm Usum)
+//            d plv = r/2B (Wsum - ip (Gg_e - 2 pm Gg_mu + pm^2 Wsum)) + 1/2 (ip (Gu_zz - 2 pm Gu_z + pm^2 Usum) - Usum)
+//
+// (oracle/dmvae_oracle.py::vade_latent_backward with the squares expanded; tests/test_vade_large_host.py holds the algebra.)
+// Launches: vade_pre (+ the tables as extra workgroups), G2, vade_rows, G1 + G3 as one grid, vade_post (+ the prior-table
+// gradients as extra workgroups).  The expanded squares cancel: bf16 operands are not an option (latent_mfma.hip).  The
+// [B, K, D] tensor is never formed, nothing is sized blocks x K x D: the scratch is linear in B D + B K + K D.  No float
+// atomics; slabs are summed in ascending order; the scores' slabs, c2 and ck are added in double (u ~ -D: a float sum would
+// cost the softmax half an ulp of D per addition).  The loss partials are written for latent_vade_nblocks() blocks as in the
+// one-kernel form, the prior-table gradient arrives COMPLETE in row 0 of dprior_partials (one partial set).
+// Device noise: latent_mfma.hip's keying -- one Philox block per four columns of a row, block index b * (Dp / 4) + d / 4,
+// normal d & 3 -- NOT latent_vade.hip's philox_normal_at(b * D + d): a different, equally valid stream.
+//
+// The evaluation (eval_clusters.hip: averaged responsibilities of `draws` samples) at these shapes is the forward half per
+// draw: vade_eval_z, G2 on the sample rows alone, vade_eval_rows; its noise is keyed exactly as vade_eval_kernel keys it.
+#include <algorithm>
+
+#include "eval_clusters.h"
+#include "latent_body.h"
+#include "latent_tables.h"
+
+namespace dmvae {
+
+struct VadeMfmaWs {        // float offsets into the caller's scratch
+    int Dp, Kp, XW, nsplit, nsplit_s;      // K slices of each half of G3 (over the batch) and of G2 (over 2D)
+    int64_t T1, T2, c2, ck, X, S, RL, W2, AC, G, total;
+};
+static VadeMfmaWs vade_mfma_layout(int Bp, int D, int K) {
+    VadeMfmaWs w;
+    w.Dp = pad64i(D); w.Kp = pad64i(K); w.XW = 2 * w.Dp + 64;
+    const int tiles = (w.Kp / 64) * (w.XW / 64);
+    int ns = 1;
+    while (ns < 32 && tiles * 2 * ns < 512 && (Bp / 64) % (2 * ns) == 0) ns *= 2;      // slices of the batch (per half): fill the chip, stay multiples of 64 rows
+    w.nsplit = ns;
+    // G2 = [2B, 2D] x [2D, K]: with few rows and clusters its grid is a handful of workgroups of a long K loop -- cut 2D.  (Shorter fmaf
+    // chains are also what keeps u accurate at D = 512; a full chip takes the one-slice form.)
+    int nss = 1;
+    while (nss < 16 && (2 * Bp / 64) * (w.Kp / 64) * nss < 512 && (2 * w.Dp / 64) % (2 * nss) == 0) nss *= 2;
+    w.nsplit_s = nss;
+    int64_t o = 0;
+    auto take = [&](int64_t n) { const int64_t r = o; o += (n + 63) / 64 * 64; return r; };
+    w.T1 = take((int64_t)w.Kp * 2 * w.Dp); w.T2 = take((int64_t)w.Kp * 2 * w.Dp);
+    w.c2 = take(w.Kp); w.ck = take(w.Kp);
+    w.X = take((int64_t)2 * Bp * w.XW); w.S = take((int64_t)nss * 2 * Bp * w.Kp); w.RL = take(Bp);
+    w.W2 = take((int64_t)2 * Bp * w.Kp); w.AC = take((int64_t)2 * Bp * 2 * w.Dp);
+    w.G = take((int64_t)2 * ns * w.Kp * w.XW);
+    w.total = o;
+    return w;
+}
+
+static int g_vade_force_mfma = 0;               // debug knob (dmvae_debug_set_knob 22): this form at every shape (without the caller's scratch: DMVAE_EINVAL)
+void latent_vade_force_mfma(int v) { g_vade_force_mfma = v; }
+bool latent_vade_mfma_needed(int D, int K) { return latent_vade_lds_bytes(D, K) > 60 * 1024; }
+bool latent_vade_mfma_forced() { return g_vade_force_mfma != 0; }
+int64_t latent_vade_mfma_ws_bytes(int B_pad, int D, int K, int* n_slabs) {
+    const VadeMfmaWs w = vade_mfma_layout(B_pad, D, K);
+    if (n_slabs) *n_slabs = 2 * w.nsplit;
+    return 4 * w.total;
+}
+
+struct VadeMfmaArgs {
+    dmvae_latent_args a;
+    VadeMfmaWs w;
+    float* ws;
+};
+
+__global__ __launch_bounds__(256) void vade_tables_kernel(const float* pm, const float* plv, int K, int D, VadeMfmaWs w, float* ws) {
+    __shared__ float tred[8];
+    latent_tables_block((int)blockIdx.x, pm, plv, K, D, w.Kp, w.Dp, ws + w.T1, ws + w.T2, ws + w.c2, ws + w.ck, tred);
+}
+
+// ---- rows, before the GEMMs.  16 lanes per row, 16 rows per 256-thread block; a lane owns quads of columns.
+__global__ __launch_bounds__(256) void vade_pre_kernel(VadeMfmaArgs L, int nrow_blocks) {
+    const dmvae_latent_args& a = L.a;
+    if ((int)blockIdx.x >= nrow_blocks) {        // extra workgroups: the prior tables as GEMM operands
+        __shared__ float tred[8];
+        latent_tables_block((int)blockIdx.x - nrow_blocks, a.prior_means, a.prior_log_vars, a.K, a.D, L.w.Kp, L.w.Dp, L.ws + L.w.T1, L.ws + L.w.T2,
+                            L.ws + L.w.c2, L.ws + L.w.ck, tred);
+        return;
+    }
+    const int lane16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
+    const int D = a.D, Dp = L.w.Dp, XW = L.w.XW;
+    const dmvae_state* st = reinterpret_cast<const dmvae_state*>(a.state);
+    const uint64_t nstep = st ? st->noise_step : a.noise_step;
+    const int b = blockIdx.x * 16 + rsub;
+    const bool valid = b < a.B;
+    const int64_t br = valid ? b : 0;            // loads of a pad row read row 0 (unconditional loads; the values are not used)
+    float* Xm = L.ws + L.w.X + (int64_t)b * XW;
+    float* Xz = L.ws + L.w.X + ((int64_t)a.B_pad + b) * XW;
+    const float* mrow = a.mean + br * a.ld_mean;
+    const float* vrow = a.log_var + br * a.ld_log_var;
+    const float* erow = a.eps ? a.eps + br * a.ld_eps : nullptr;
+    const bool vec = (D % 4 == 0) && (a.ld_mean % 4 == 0) && (a.ld_log_var % 4 == 0) && (a.ld_g % 4 == 0) && (a.ld_Z % 4 == 0) &&
+                     (!a.eps || a.ld_eps % 4 == 0) && (!a.Z_f32 || a.ld_Zf % 4 == 0);
+    float lvsum = 0.f;
+    for (int q4 = lane16; q4 < Dp / 4; q4 += 16) {
+        const int d0 = 4 * q4;
+        float mu[4] = {0.f, 0.f, 0.f, 0.f}, lv[4] = {0.f, 0.f, 0.f, 0.f}, ep[4] = {0.f, 0.f, 0.f, 0.f};
+        if (vec) {                               // (D % 4 == 0: a quad is inside the row or outside it)
+            const int off = d0 < D ? d0 : 0;
+            const float4 m4 = *reinterpret_cast<const float4*>(mrow + off);
+            const float4 l4 = *reinterpret_cast<const float4*>(vrow + off);
+            const float4 e4 = erow ? *reinterpret_cast<const float4*>(erow + off) : make_float4(0.f, 0.f, 0.f, 0.f);
+            mu[0] = m4.x; mu[1] = m4.y; mu[2] = m4.z; mu[3] = m4.w;
+            lv[0] = l4.x; lv[1] = l4.y; lv[2] = l4.z; lv[3] = l4.w;
+            ep[0] = e4.x; ep[1] = e4.y; ep[2] = e4.z; ep[3] = e4.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int off = d0 + j < D ? d0 + j : 0;
+                mu[j] = mrow[off]; lv[j] = vrow[off];
+                if (erow) ep[j] = erow[off];
+            }
+        }
+        if (valid && d0 < D && !a.eps) philox_normal4(a.seed, nstep, 0u, (uint64_t)b * (Dp / 4) + q4, ep);
+        float z[4], cl[4], x1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool ok = valid && d0 + j < D;
+            const float e = __expf(lv[j]), sd = __expf(0.5f * lv[j]);
+            z[j] = ok ? mu[j] + sd * ep[j] : 0.f;
+            cl[j] = ok ? ep[j] * 0.5f * sd : 0.f;
+            x1[j] = ok ? e + mu[j] * mu[j] : 0.f;
+            mu[j] = ok ? mu[j] : 0.f;
+            lvsum += ok ? lv[j] : 0.f;
+        }
+        *reinterpret_cast<float4*>(Xm + d0) = make_float4(x1[0], x1[1], x1[2], x1[3]);
+        *reinterpret_cast<float4*>(Xm + Dp + d0) = make_float4(mu[0], mu[1], mu[2], mu[3]);
+        *reinterpret_cast<float4*>(Xz + d0) = make_float4(z[0] * z[0], z[1] * z[1], z[2] * z[2], z[3] * z[3]);
+        *reinterpret_cast<float4*>(Xz + Dp + d0) = make_float4(z[0], z[1], z[2], z[3]);
+        // outputs: Z (act dtype, pad columns up to ld_Z zeroed: they are K padding of the first decoder GEMM), f32 copy, coefficient
+        if (vec && d0 + 4 <= a.ld_Z) {
+            if (a.act_dtype == DMVAE_BF16) {
+                uint2 pk;
+                pk.x = pack2bf(z[0], z[1]); pk.y = pack2bf(z[2], z[3]);
+                *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(a.Z_act) + (int64_t)b * a.ld_Z + d0) = pk;
+            } else *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.Z_act) + (int64_t)b * a.ld_Z + d0) = make_float4(z[0], z[1], z[2], z[3]);
+            if (d0 < D) {
+                if (a.Z_f32) *reinterpret_cast<float4*>(a.Z_f32 + (int64_t)b * a.ld_Zf + d0) = make_float4(z[0], z[1], z[2], z[3]);
+                *reinterpret_cast<float4*>(a.clv + (int64_t)b * a.ld_g + d0) = make_float4(cl[0], cl[1], cl[2], cl[3]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int d = d0 + j;
+                if (d < a.ld_Z) {
+                    if (a.act_dtype == DMVAE_BF16) reinterpret_cast<bf16_t*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = f2bf(z[j]);
+                    else reinterpret_cast<float*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = z[j];
+                }
+                if (d < D) {
+                    if (a.Z_f32) a.Z_f32[(int64_t)b * a.ld_Zf + d] = z[j];
+                    a.clv[(int64_t)b * a.ld_g + d] = cl[j];
+                }
+            }
+        }
+    }
+    for (int d = Dp + lane16; d < a.ld_Z; d += 16) {      // (a Z buffer wider than D padded to 64)
+        if (a.act_dtype == DMVAE_BF16) reinterpret_cast<bf16_t*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = 0;
+        else reinterpret_cast<float*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = 0.f;
+    }
+    for (int c = lane16; c < 64; c += 16) {                // the ones column: G3 then also yields sum_b gamma and sum_b du
+        Xm[2 * Dp + c] = (c == 0 && valid) ? 1.f : 0.f;
+        Xz[2 * Dp + c] = (c == 0 && valid) ? 1.f : 0.f;
+    }
+    lvsum = row_sum16(lvsum);
+    if (lane16 == 0) L.ws[L.w.RL + b] = lvsum;
+}
+
+// S_k + c2_k + ck_k of four clusters k0 .. k0 + 3 of one row from the K-slice slabs, in double (slabs in ascending order).  k0 < Kp: the pad
+// columns of S, c2 and ck exist (zeros)
+__device__ __forceinline__ void vade_score4(const float* S0, int64_t sstr, int nss, const float* c2, const float* ck, int k0, double v[4]) {
+    const float4 s0 = *reinterpret_cast<const float4*>(S0 + k0);
+    v[0] = (double)s0.x; v[1] = (double)s0.y; v[2] = (double)s0.z; v[3] = (double)s0.w;
+    for (int sl = 1; sl < nss; ++sl) {
+        const float4 t = *reinterpret_cast<const float4*>(S0 + sl * sstr + k0);
+        v[0] += (double)t.x; v[1] += (double)t.y; v[2] += (double)t.z; v[3] += (double)t.w;
+    }
+    const float4 p = *reinterpret_cast<const float4*>(c2 + k0), q = *reinterpret_cast<const float4*>(ck + k0);
+    v[0] = v[0] + (double)p.x + (double)q.x; v[1] = v[1] + (double)p.y + (double)q.y;
+    v[2] = v[2] + (double)p.z + (double)q.z; v[3] = v[3] + (double)p.w + (double)q.w;
+}
+
+// one row of responsibilities to the caller's [rows][ld] array: 16 bytes where the quad is whole and aligned
+__device__ __forceinline__ void vade_store_w4(float* row, bool vecw, int k0, int K, const float g[4]) {
+    if (vecw && k0 + 4 <= K) *reinterpret_cast<float4*>(row + k0) = make_float4(g[0], g[1], g[2], g[3]);
+    else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (k0 + j < K) row[k0 + j] = g[j];
+    }
+}
+
+// ---- rows, between G2 and G1 / G3: responsibilities, both KL terms, dL/du.  A lane owns the QUADS of clusters k0 = 4 (lane16 + 16 i): every access
+// to the scratch is 16 bytes wide.  A row's W2 entries are its staging for T, then G (each lane reads back only what it wrote).
+__global__ __launch_bounds__(256) void vade_rows_kernel(VadeMfmaArgs L) {
+    const dmvae_latent_args& a = L.a;
+    const int lane16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
+    const int K = a.K, Kp = L.w.Kp, nss = L.w.nsplit_s;
+    const dmvae_state* st = reinterpret_cast<const dmvae_state*>(a.state);
+    const float klr = st ? st->kl_ratio : a.kl_ratio;
+    const float rB = klr * a.inv_B, logK = __logf((float)K);
+    const int b = blockIdx.x * 16 + rsub;
+    const bool valid = b < a.B;
+    const int64_t sstr = (int64_t)2 * a.B_pad * Kp;
+    const float* Sm = L.ws + L.w.S + (int64_t)b * Kp;
+    const float* Sz = L.ws + L.w.S + ((int64_t)a.B_pad + b) * Kp;
+    const float* c2 = L.ws + L.w.c2;
+    const float* ck = L.ws + L.w.ck;
+    float* gam = L.ws + L.w.W2 + (int64_t)b * Kp;
+    float* dus = L.ws + L.w.W2 + ((int64_t)a.B_pad + b) * Kp;
+    const float base = L.ws[L.w.RL + b] + (float)a.D;
+    const bool vecw = a.weights && a.ld_w % 4 == 0 && (reinterpret_cast<uintptr_t>(a.weights) & 15) == 0;
+    __shared__ float red[32];
+
+    double mxd = -INFINITY;
+    float tmin = INFINITY;
+    for (int k0 = 4 * lane16; k0 < K; k0 += 64) {
+        double uz[4], sm[4];
+        vade_score4(Sz, sstr, nss, c2, ck, k0, uz);
+        vade_score4(Sm, sstr, nss, c2, ck, k0, sm);
+        float T[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool in = k0 + j < K;
+            T[j] = in ? (float)sm[j] - base : 0.f;
+            if (in) { mxd = fmax(mxd, -0.5 * uz[j]); tmin = fminf(tmin, T[j]); }
+        }
+        *reinterpret_cast<float4*>(dus + k0) = make_float4(T[0], T[1], T[2], T[3]);      // T_k for now
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) { mxd = fmax(mxd, __shfl_xor(mxd, o, 16)); tmin = fminf(tmin, __shfl_xor(tmin, o, 16)); }
+    float se = 0.f;
+    for (int k0 = 4 * lane16; k0 < K; k0 += 64) {
+        double uz[4];
+        vade_score4(Sz, sstr, nss, c2, ck, k0, uz);
+        float ex[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            ex[j] = k0 + j < K ? __expf((float)(-0.5 * uz[j] - mxd)) : 0.f;
+            se += ex[j];
+        }
+        *reinterpret_cast<float4*>(gam + k0) = make_float4(ex[0], ex[1], ex[2], ex[3]);
+    }
+    se = row_sum16(se);
+    float sgG = 0.f, klz = 0.f, klc = 0.f;
+    for (int k0 = 4 * lane16; k0 < K; k0 += 64) {
+        const float4 e4 = *reinterpret_cast<const float4*>(gam + k0), T4 = *reinterpret_cast<const float4*>(dus + k0);
+        const float ex[4] = {e4.x, e4.y, e4.z, e4.w}, T[4] = {T4.x, T4.y, T4.z, T4.w};
+        float g[4], G[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool in = k0 + j < K;
+            g[j] = valid && in ? ex[j] / se : 0.f;
+            const float lg = __logf(g[j] + 1e-20f);
+            // G up to a constant of the row: du = gamma (G - sum gamma G) does not see it in exact arithmetic, but sum_k gamma_k is 1 only to
+            // an ulp, and sum_k du_k = (1 - sum gamma) sum gamma G then leaks into dZ_lat times z.  T ~ D makes G ~ r/B D/2: taken relative
+            // to the row's smallest T (and without log K) the leak is of the size of the DIFFERENCES of G, as du itself.
+            G[j] = in ? rB * (0.5f * (T[j] - tmin) + lg + g[j] / (g[j] + 1e-20f)) : 0.f;
+            if (in) {
+                sgG += g[j] * G[j];
+                klz += 0.5f * g[j] * T[j];
+                klc += g[j] * (lg + logK);
+            }
+        }
+        *reinterpret_cast<float4*>(gam + k0) = make_float4(g[0], g[1], g[2], g[3]);
+        *reinterpret_cast<float4*>(dus + k0) = make_float4(G[0], G[1], G[2], G[3]);      // G for now
+        if (a.weights) vade_store_w4(a.weights + (int64_t)b * a.ld_w, vecw, k0, K, g);
+    }
+    sgG = row_sum16(sgG); klz = row_sum16(klz); klc = row_sum16(klc);
+    for (int k0 = 4 * lane16; k0 < Kp; k0 += 64) {
+        float4 du = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (k0 < K) {                                                        // (gamma of a pad cluster inside the quad is already 0)
+            const float4 g4 = *reinterpret_cast<const float4*>(gam + k0), G4 = *reinterpret_cast<const float4*>(dus + k0);
+            du.x = g4.x * (G4.x - sgG); du.y = g4.y * (G4.y - sgG); du.z = g4.z * (G4.z - sgG); du.w = g4.w * (G4.w - sgG);
+        } else *reinterpret_cast<float4*>(gam + k0) = du;                    // pad clusters: zero rows of G3, zero terms of G1
+        *reinterpret_cast<float4*>(dus + k0) = du;
+    }
+    if (lane16 == 0) { red[rsub] = valid ? klz : 0.f; red[16 + rsub] = valid ? klc : 0.f; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float z = 0.f, c = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { z += red[i]; c += red[16 + i]; }
+        a.loss_partials[2 * blockIdx.x] = z;
+        a.loss_partials[2 * blockIdx.x + 1] = c;
+    }
+}
+
+// ---- rows, after the GEMMs; workgroups >= nrow_blocks: the prior-table gradients from the G slabs
+__global__ __launch_bounds__(256) void vade_post_kernel(VadeMfmaArgs L, int nrow_blocks) {
+    const dmvae_latent_args& a = L.a;
+    const int D = a.D, K = a.K, Dp = L.w.Dp, Kp = L.w.Kp, XW = L.w.XW;
+    const dmvae_state* st = reinterpret_cast<const dmvae_state*>(a.state);
+    const float klr = st ? st->kl_ratio : a.kl_ratio;
+    const float rB = klr * a.inv_B, rB2 = 0.5f * rB;
+    if ((int)blockIdx.x >= nrow_blocks) {
+        const int64_t KD = (int64_t)K * D;
+        const int ns = L.w.nsplit;
+        for (int64_t idx = (int64_t)((int)blockIdx.x - nrow_blocks) * 256 + threadIdx.x; idx < KD; idx += (int64_t)((int)gridDim.x - nrow_blocks) * 256) {
+            const int k = (int)(idx / D), d = (int)(idx - (int64_t)k * D);
+            float ge = 0.f, gm = 0.f, wsum = 0.f, gzz = 0.f, gz = 0.f, usum = 0.f;
+            for (int s = 0; s < ns; ++s) {                                   // slabs in ascending order: mean rows, then sample rows
+                const float* g = L.ws + L.w.G + ((int64_t)s * Kp + k) * XW;
+                ge += g[d]; gm += g[Dp + d]; wsum += g[2 * Dp];
+            }
+            for (int s = ns; s < 2 * ns; ++s) {
+                const float* g = L.ws + L.w.G + ((int64_t)s * Kp + k) * XW;
+                gzz += g[d]; gz += g[Dp + d]; usum += g[2 * Dp];
+            }
+            const float ip = L.ws[L.w.T1 + (int64_t)k * 2 * Dp + d];
+            const float pmv = a.prior_means[idx];
+            a.dprior_partials[idx] = -rB * ip * (gm - pmv * wsum) + ip * (gz - pmv * usum);
+            a.dprior_partials[KD + idx] = rB2 * (wsum - ip * (ge - 2.f * pmv * gm + pmv * pmv * wsum)) +
+                                          0.5f * (ip * (gzz - 2.f * pmv * gz + pmv * pmv * usum) - usum);
+        }
+        return;
+    }
+    const int lane16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
+    const int b = blockIdx.x * 16 + rsub;
+    const bool valid = b < a.B;
+    const int64_t br = valid ? b : 0;
+    const float* ACm = L.ws + L.w.AC + (int64_t)b * 2 * Dp;
+    const float* ACu = L.ws + L.w.AC + ((int64_t)a.B_pad + b) * 2 * Dp;
+    const float* Xm = L.ws + L.w.X + (int64_t)b * XW;
+    const float* Xz = L.ws + L.w.X + ((int64_t)a.B_pad + b) * XW;
+    const float* vrow = a.log_var + br * a.ld_log_var;
+    const float* crow = a.clv + (int64_t)b * a.ld_g;      // what vade_pre wrote (columns < D of every row)
+    const bool vec = D % 4 == 0 && a.ld_log_var % 4 == 0 && a.ld_g % 4 == 0;
+    for (int q4 = lane16; q4 < (D + 3) / 4; q4 += 16) {
+        const int d0 = 4 * q4;
+        const float4 A4 = *reinterpret_cast<const float4*>(ACm + d0), C4 = *reinterpret_cast<const float4*>(ACm + Dp + d0);
+        const float4 U4 = *reinterpret_cast<const float4*>(ACu + d0), V4 = *reinterpret_cast<const float4*>(ACu + Dp + d0);
+        const float4 M4 = *reinterpret_cast<const float4*>(Xm + Dp + d0), Z4 = *reinterpret_cast<const float4*>(Xz + Dp + d0);
+        const float A[4] = {A4.x, A4.y, A4.z, A4.w}, Cc[4] = {C4.x, C4.y, C4.z, C4.w}, Au[4] = {U4.x, U4.y, U4.z, U4.w}, Cu[4] = {V4.x, V4.y, V4.z, V4.w};
+        const float mu[4] = {M4.x, M4.y, M4.z, M4.w}, z[4] = {Z4.x, Z4.y, Z4.z, Z4.w};
+        float lv[4], cl[4];
+        if (vec) {
+            const float4 l4 = *reinterpret_cast<const float4*>(vrow + d0), c4 = *reinterpret_cast<const float4*>(crow + d0);
+            lv[0] = l4.x; lv[1] = l4.y; lv[2] = l4.z; lv[3] = l4.w;
+            cl[0] = c4.x; cl[1] = c4.y; cl[2] = c4.z; cl[3] = c4.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int off = d0 + j < D ? d0 + j : 0;
+                lv[j] = vrow[off]; cl[j] = crow[off];
+            }
+        }
+        float gm[4], gl[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float dzl = -(z[j] * Au[j] - Cu[j]);
+            gm[j] = valid ? rB * (mu[j] * A[j] - Cc[j]) + dzl : 0.f;
+            gl[j] = valid ? rB2 * (__expf(lv[j]) * A[j] - 1.f) + dzl * cl[j] : 0.f;
+        }
+        if (vec) {
+            *reinterpret_cast<float4*>(a.gmu + (int64_t)b * a.ld_g + d0) = make_float4(gm[0], gm[1], gm[2], gm[3]);
+            *reinterpret_cast<float4*>(a.glv + (int64_t)b * a.ld_g + d0) = make_float4(gl[0], gl[1], gl[2], gl[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (d0 + j < D) {
+                    a.gmu[(int64_t)b * a.ld_g + d0 + j] = gm[j];
+                    a.glv[(int64_t)b * a.ld_g + d0 + j] = gl[j];
+                }
+        }
+    }
+}
+
+static int vade_score_gemm(hipStream_t s, const VadeMfmaWs& w, float* ws, int rows) {
+    // G2 (dX layout): rows x [2 Dp] . ([Kp] x [2 Dp])^T, its K slices into slabs
+    const GemmArgs g2 = f32_problem(rows, w.Kp, 2 * w.Dp, ws + w.X, w.XW, ws + w.T2, 2 * w.Dp, ws + w.S, w.Kp, w.nsplit_s, (int64_t)rows * w.Kp);
+    return gemm_f32_dispatch(s, DMVAE_GEMM_DX, g2, w.nsplit_s);
+}
+
+int latent_vade_mfma_launch(hipStream_t s, const dmvae_latent_args* a, float* ws, int64_t ws_bytes) {
+    const VadeMfmaWs w = vade_mfma_layout(a->B_pad, a->D, a->K);
+    if (!ws || 4 * w.total > ws_bytes) {
+        set_error("dmvae_latent_fwd (VaDE): K=%d D=%d takes the large-table form, which needs mfma_ws of dmvae_latent_vade_ws_bytes() = %lld bytes (got %lld)",
+                  a->K, a->D, (long long)(4 * w.total), (long long)(ws ? ws_bytes : 0));
+        return DMVAE_EINVAL;
+    }
+    VadeMfmaArgs L;
+    L.a = *a; L.w = w; L.ws = ws;
+    const int nrb = a->B_pad / 16, Bp2 = 2 * a->B_pad;
+    const double BD = (double)a->B * a->D, BK = (double)a->B * a->K;
+    {   // the prior-table operands ride as Kp extra workgroups of the row kernel
+        ProfScope ps(s, "vade_pre", 0.0, 4.0 * (BD * (2.0 + (a->eps ? 1.0 : 0.0) + 4.0 + 2.0 + 1.0)) + 16.0 * a->K * a->D);
+        DMVAE_LAUNCH(vade_pre_kernel, dim3(nrb + w.Kp), dim3(256), 0, s, L, nrb);
+    }
+    int rc = check_launch("vade_pre");
+    if (rc) return rc;
+    {
+        ProfScope ps(s, "vade_gemm_f32", 2.0 * Bp2 * (double)w.Kp * 2.0 * w.Dp, 4.0 * Bp2 * (2.0 * w.Dp + (double)w.nsplit_s * w.Kp));
+        rc = vade_score_gemm(s, w, ws, Bp2);
+    }
+    if (rc) return rc;
+    {
+        ProfScope ps(s, "vade_rows", 0.0, 4.0 * BK * (4.0 * w.nsplit_s + 3.0));
+        DMVAE_LAUNCH(vade_rows_kernel, dim3(nrb), dim3(256), 0, s, L);
+    }
+    rc = check_launch("vade_rows");
+    if (rc) return rc;
+    {
+        ProfScope ps(s, "vade_gemm_f32", 2.0 * Bp2 * (double)w.Kp * (2.0 * w.Dp + w.XW), 4.0 * Bp2 * (2.0 * w.Kp + w.XW + 2.0 * w.Dp));
+        // G1 (forward layout) and G3 (dW layout, 2 nsplit batch slices into slabs) read only what the kernels above wrote: one grid
+        // (gemm_f32_trio with its dX problem absent)
+        const GemmArgs g1 = f32_problem(Bp2, 2 * w.Dp, w.Kp, ws + w.W2, w.Kp, ws + w.T1, 2 * w.Dp, ws + w.AC, 2 * w.Dp, 1, 0);
+        const GemmArgs none = f32_problem(0, 64, 16, nullptr, 0, nullptr, 0, nullptr, 0, 1, 0);
+        const GemmArgs g3 = f32_problem(w.Kp, w.XW, Bp2, ws + w.W2, w.Kp, ws + w.X, w.XW, ws + w.G, w.XW, 2 * w.nsplit, (int64_t)w.Kp * w.XW);
+        rc = gemm_f32_trio(s, g1, 1, none, 1, g3, 2 * w.nsplit);
+    }
+    if (rc) return rc;
+    {
+        const int extra = (int)std::min<int64_t>(256, ((int64_t)a->K * a->D + 255) / 256);
+        ProfScope ps(s, "vade_post", 0.0, 4.0 * (BD * (4.0 + 2.0 + 2.0 + 2.0)) + 8.0 * w.nsplit * w.Kp * w.XW);
+        DMVAE_LAUNCH(vade_post_kernel, dim3(nrb + extra), dim3(256), 0, s, L, nrb);
+    }
+    return check_launch("vade_post");
+}
+
+// ---- evaluation: averaged responsibilities of `draws` samples (eval_clusters.hip), the forward half per draw
+struct VadeEvalMfma {
+    VadeEvalArgs a;
+    VadeMfmaWs w;
+    float* ws;
+};
+
+// z of draw j as the rows of G2's A operand: [z^2 | z], pad rows and pad columns zero.  A lane owns quads of columns (16-byte accesses where the
+// caller's rows allow it); the noise keeps vade_eval_kernel's per-element keying
+__global__ __launch_bounds__(256) void vade_eval_z_kernel(VadeEvalMfma L, int j) {
+    const VadeEvalArgs& a = L.a;
+    const int lane16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
+    const int D = a.D, Dp = L.w.Dp;
+    const int b = blockIdx.x * 16 + rsub;
+    const bool valid = b < a.rows.n_valid;
+    const int64_t br = valid ? b : 0;
+    float* Xz = L.ws + L.w.X + (int64_t)b * L.w.XW;
+    const uint64_t pos = (uint64_t)(a.rows.first + b);
+    const float* mrow = a.mean + br * a.ld_mean;
+    const float* vrow = a.log_var + br * a.ld_log_var;
+    const float* erow = a.eps ? a.eps + ((int64_t)j * a.rows.n_valid + br) * a.ld_eps : nullptr;
+    const bool vec = D % 4 == 0 && a.ld_mean % 4 == 0 && a.ld_log_var % 4 == 0 && (!a.eps || a.ld_eps % 4 == 0) &&
+                     ((reinterpret_cast<uintptr_t>(a.mean) | reinterpret_cast<uintptr_t>(a.log_var) | reinterpret_cast<uintptr_t>(a.eps)) & 15) == 0;
+    for (int d0 = 4 * lane16; d0 < Dp; d0 += 64) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (valid && d0 < D) {
+            float mu[4], lv[4], ep[4];
+            if (vec) {
+                const float4 m4 = *reinterpret_cast<const float4*>(mrow + d0), l4 = *reinterpret_cast<const float4*>(vrow + d0);
+                mu[0] = m4.x; mu[1] = m4.y; mu[2] = m4.z; mu[3] = m4.w;
+                lv[0] = l4.x; lv[1] = l4.y; lv[2] = l4.z; lv[3] = l4.w;
+                if (erow) {
+                    const float4 e4 = *reinterpret_cast<const float4*>(erow + d0);
+                    ep[0] = e4.x; ep[1] = e4.y; ep[2] = e4.z; ep[3] = e4.w;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int off = d0 + i < D ? d0 + i : 0;
+                    mu[i] = mrow[off]; lv[i] = vrow[off];
+                    if (erow) ep[i] = erow[off];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (!erow) ep[i] = philox_normal_at(a.seed, a.counter, EVAL_PHILOX_STREAM, ((uint64_t)j * (uint64_t)a.rows.n_rows + pos) * (uint64_t)D + (d0 + i < D ? d0 + i : 0));
+                z[i] = d0 + i < D ? mu[i] + __expf(0.5f * lv[i]) * ep[i] : 0.f;
+            }
+        }
+        *reinterpret_cast<float4*>(Xz + d0) = make_float4(z[0] * z[0], z[1] * z[1], z[2] * z[2], z[3] * z[3]);
+        *reinterpret_cast<float4*>(Xz + Dp + d0) = make_float4(z[0], z[1], z[2], z[3]);
+    }
+}
+
+// gamma of draw j added to the row's sum (W2 rows [0, B_pad); rows [B_pad, 2 B_pad) are staging); the last draw writes the average.  Quads of
+// clusters per lane, as vade_rows
+__global__ __launch_bounds__(256) void vade_eval_rows_kernel(VadeEvalMfma L, int j) {
+    const VadeEvalArgs& a = L.a;
+    const int lane16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
+    const int K = a.K, Kp = L.w.Kp, nss = L.w.nsplit_s;
+    const int b = blockIdx.x * 16 + rsub;
+    const bool valid = b < a.rows.n_valid;
+    const int64_t sstr = (int64_t)a.B_pad * Kp;
+    const float* Sz = L.ws + L.w.S + (int64_t)b * Kp;
+    const float* c2 = L.ws + L.w.c2;
+    const float* ck = L.ws + L.w.ck;
+    float* acc = L.ws + L.w.W2 + (int64_t)b * Kp;
+    float* exs = L.ws + L.w.W2 + ((int64_t)a.B_pad + b) * Kp;
+    const bool vecw = a.ld_w % 4 == 0 && (reinterpret_cast<uintptr_t>(a.w) & 15) == 0;
+    double mxd = -INFINITY;
+    for (int k0 = 4 * lane16; k0 < K; k0 += 64) {
+        double uz[4];
+        vade_score4(Sz, sstr, nss, c2, ck, k0, uz);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (k0 + i < K) mxd = fmax(mxd, -0.5 * uz[i]);
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) mxd = fmax(mxd, __shfl_xor(mxd, o, 16));
+    float se = 0.f;
+    for (int k0 = 4 * lane16; k0 < K; k0 += 64) {
+        double uz[4];
+        vade_score4(Sz, sstr, nss, c2, ck, k0, uz);
+        float ex[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            ex[i] = k0 + i < K ? __expf((float)(-0.5 * uz[i] - mxd)) : 0.f;
+            se += ex[i];
+        }
+        *reinterpret_cast<float4*>(exs + k0) = make_float4(ex[0], ex[1], ex[2], ex[3]);
+    }
+    se = row_sum16(se);
+    const float nd = (float)a.draws;
+    for (int k0 = 4 * lane16; k0 < K; k0 += 64) {
+        const float4 e4 = *reinterpret_cast<const float4*>(exs + k0);
+        float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (j) s4 = *reinterpret_cast<const float4*>(acc + k0);
+        const float sum[4] = {s4.x + e4.x / se, s4.y + e4.y / se, s4.z + e4.z / se, s4.w + e4.w / se};
+        *reinterpret_cast<float4*>(acc + k0) = make_float4(sum[0], sum[1], sum[2], sum[3]);
+        if (j == a.draws - 1 && valid) {
+            const float avg[4] = {sum[0] / nd, sum[1] / nd, sum[2] / nd, sum[3] / nd};
+            vade_store_w4(a.w + (int64_t)b * a.ld_w, vecw, k0, K, avg);
+        }
+    }
+}
+
+int vade_eval_mfma_launch(hipStream_t s, const VadeEvalArgs& a) {
+    const VadeMfmaWs w = vade_mfma_layout(a.B_pad, a.D, a.K);
+    VadeEvalMfma L;
+    L.a = a; L.w = w; L.ws = a.ws;
+    const int nrb = a.B_pad / 16;
+    const double n = a.rows.n_valid;
+    {
+        ProfScope ps(s, "vade_tables", 0.0, 24.0 * a.K * a.D);
+        DMVAE_LAUNCH(vade_tables_kernel, dim3(w.Kp), dim3(256), 0, s, a.prior_means, a.prior_log_vars, a.K, a.D, w, a.ws);
+    }
+    int rc = check_launch("vade_tables");
+    if (rc) return rc;
+    for (int j = 0; j < a.draws; ++j) {
+        {
+            ProfScope ps(s, "vade_eval_z", 0.0, 4.0 * n * a.D * (4.0 + (a.eps ? 1.0 : 0.0)));
+            DMVAE_LAUNCH(vade_eval_z_kernel, dim3(nrb), dim3(256), 0, s, L, j);
+        }
+        if ((rc = check_launch("vade_eval_z"))) return rc;
+        {
+            ProfScope ps(s, "vade_gemm_f32", 2.0 * a.B_pad * (double)w.Kp * 2.0 * w.Dp, 4.0 * a.B_pad * (2.0 * w.Dp + (double)w.nsplit_s * w.Kp));
+            rc = vade_score_gemm(s, w, a.ws, a.B_pad);
+        }
+        if (rc) return rc;
+        {
+            ProfScope ps(s, "vade_eval_rows", 0.0, 4.0 * n * a.K * (2.0 * w.nsplit_s + 4.0));
+            DMVAE_LAUNCH(vade_eval_rows_kernel, dim3(nrb), dim3(256), 0, s, L, j);
+        }
+        if ((rc = check_launch("vade_eval_rows"))) return rc;
+    }
+    return confusion_add_launch(s, a.w, a.ld_w, a.K, a.rows);      // the same arg-max and count as vade_eval_kernel's
+}
+
+}  // namespace dmvae

@@ -28,7 +28,7 @@ TRUNK_MLP, TRUNK_CNN = 0, 1
 MODEL_DMVAE, MODEL_VADE = 0, 1
 
 EXPORTS = [
-    "dmvae_gemm", "dmvae_gemm_partials", "dmvae_gemm_grouped_dw", "dmvae_gemm_grouped", "dmvae_gemm_grouped_dw_adam", "dmvae_plan_train_step", "dmvae_latent_ws_bytes", "dmvae_latent_nblocks_vade",
+    "dmvae_gemm", "dmvae_gemm_partials", "dmvae_gemm_grouped_dw", "dmvae_gemm_grouped", "dmvae_gemm_grouped_dw_adam", "dmvae_plan_train_step", "dmvae_latent_ws_bytes", "dmvae_latent_nblocks_vade", "dmvae_latent_vade_ws_bytes",
     "dmvae_plan_forward_backward_stage", "dmvae_plan_grad_buckets", "dmvae_plan_set_stage_groups", "dmvae_plan_update_range",
 "dmvae_latent_nblocks", "dmvae_latent_fwd", "dmvae_heads_latent_fwd", "dmvae_heads_latent_ok", "dmvae_heads_latent_kslice_floats",
     "dmvae_recon_fwd_bwd", "dmvae_recon_nblocks", "dmvae_colsum", "dmvae_loss_finalize",
@@ -195,6 +195,7 @@ def _load():
         "dmvae_latent_nblocks": [i32, i32, i32],
         "dmvae_latent_nblocks_vade": [i32],
         "dmvae_latent_ws_bytes": [i32, i32, i32, i32],
+        "dmvae_latent_vade_ws_bytes": [i32, i32, i32, i32, P(C.c_int)],
         "dmvae_latent_fwd": [vp, P(LatentArgs)],
         "dmvae_heads_latent_fwd": [vp, P(HeadsArgs), P(LatentArgs)],
         "dmvae_heads_latent_ok": [i32, i32, i32, i32, i32, i32, i32],
@@ -261,6 +262,7 @@ def _load():
         fn.restype = C.c_int
     lib.dmvae_last_error.restype = C.c_char_p
     lib.dmvae_latent_ws_bytes.restype = C.c_int64
+    lib.dmvae_latent_vade_ws_bytes.restype = C.c_int64
     lib.dmvae_heads_latent_kslice_floats.restype = C.c_int64
     lib.dmvae_gmm_ws_bytes.restype = C.c_int64
     lib.dmvae_gmm_seed_ws_bytes.restype = C.c_int64

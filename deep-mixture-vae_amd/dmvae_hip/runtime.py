@@ -846,6 +846,11 @@ def latent_eval(mean, log_var, logits, prior_means, prior_log_vars, eps=None, gu
     a.gmu, a.glv, a.clv, a.ld_g = gmu.data_ptr(), glv.data_ptr(), clv.data_ptr(), ldD
     a.dlogits_act, a.ld_dl = dlg.data_ptr(), ldK
     a.dprior_partials, a.loss_partials = dpri.data_ptr(), lp.data_ptr()
+    if mode == "vade":          # prior tables past the one-kernel form's LDS: the large-table form and its scratch (csrc/latent_vade_mfma.hip)
+        nb = int(lib.dmvae_latent_vade_ws_bytes(Bp, D, K, 0, None))
+        if nb:
+            ws = torch.empty(nb // 4, dtype=torch.float32, device=dev)
+            a.mfma_ws, a.mfma_ws_bytes = ws.data_ptr(), nb
     check(lib.dmvae_latent_fwd(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.byref(a)), "dmvae_latent_fwd")
     torch.cuda.synchronize(dev)
     return dict(Z=Z[:B, :D].cpu().numpy(), weights=w[:B].cpu().numpy(),

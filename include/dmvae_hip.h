@@ -185,6 +185,16 @@ int dmvae_latent_nblocks(int B_pad, int D, int K);
  * gradients through them included; logits / gumbel / dlogits_act are ignored (may be NULL); `weights` receives the
  * responsibilities.  It writes dmvae_latent_nblocks_vade(B_pad) = B_pad / 16 blocks of partials. */
 int dmvae_latent_nblocks_vade(int B_pad);
+/* Prior tables past the LDS of that kernel -- 4 (2 K (D + 1) + 33 K + 64 (D + 1) + 32) bytes > 60 KiB: D = 256 at any K, D = 128 from
+ * K = 11 on -- take the large-table form (csrc/latent_vade_mfma.hip: the contractions as exact-f32 MFMA GEMMs between row kernels),
+ * for any D and K (mode 2 is dispatched before, and shares none of, the LDS limit of modes 0 and 1; what bounds it is the memory for
+ * its scratch).  It needs scratch in mfma_ws / mfma_ws_bytes (without it: DMVAE_EINVAL), linear in B D + B K + K D:
+ * dmvae_latent_vade_ws_bytes, pure host arithmetic, returns its size -- 0 where the one-kernel form runs (forced = 0), or what the
+ * large-table form would need at any shape (forced = 1: debug knob 22); *n_slabs (may be NULL): the batch slabs of its two
+ * prior-table contractions together.  Loss partials as above; the prior-table gradient arrives COMPLETE in row 0 of
+ * dprior_partials.  Device noise of this form: the keying of csrc/latent_mfma.hip.  dmvae_latent_ws_bytes(.., mode 2) is
+ * dmvae_latent_vade_ws_bytes(.., 0, NULL). */
+int64_t dmvae_latent_vade_ws_bytes(int B_pad, int D, int K, int forced, int* n_slabs);
 int64_t dmvae_latent_ws_bytes(int B_pad, int D, int K, int mode);   /* 0 when the MFMA form does not apply */
 int dmvae_latent_fwd(void* stream, const dmvae_latent_args* a);
 

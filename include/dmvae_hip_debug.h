@@ -94,7 +94,13 @@ int dmvae_debug_set_tile(int bm, int bn);
  *                       bytes (1: fetches 13 % less at 8192 rows and is 2 .. 6 % slower on the step at every size: profiles/r05_dw_refetch.txt),
  *             knob 21 = K slices of the thin launches of a small batch (<= 256 rows: the dense layers with K >= 2048 and the dZ GEMM; up to 2048 rows: the fused
  *                       heads + latent launch while blocks x slices <= 256), joined by the last workgroup to arrive (GemmArgs::tick): 1 (default) slices of
- *                       512, 2 slices of 256 (0.1397 vs 0.1402 ms at 100 rows: the same), 0 none */
+ *                       512, 2 slices of 256 (0.1397 vs 0.1402 ms at 100 rows: the same), 0 none,
+ *             knob 22 = VaDE's latent stage (dmvae_latent_fwd mode 2) on the large-table form (csrc/latent_vade_mfma.hip) for shapes that fit the
+ *                       one-kernel form too (0, default: only where the one-kernel form does not fit; tests/test_gpu_vade_large.py compares the
+ *                       two forms).  The caller's dmvae_latent_args.mfma_ws must then hold dmvae_latent_vade_ws_bytes(.., forced = 1, ..) bytes:
+ *                       without them the call is DMVAE_EINVAL, it never falls back to the one-kernel form.  Plans reserve that scratch (and size
+ *                       their prior-gradient partials) by the shape alone, so while the knob is set the steps of a plan whose shape fits the
+ *                       one-kernel form fail with that DMVAE_EINVAL: the knob is for callers of dmvae_latent_fwd. */
 int dmvae_debug_set_knob(int which, int value);
 
 /* ---- the CNN trunk's kernels on caller-owned buffers (csrc/conv.hip; tests/test_gpu_conv_kernels.py) ----------

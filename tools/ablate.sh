@@ -16,6 +16,6 @@ done
 wait
 for n in "$@"; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/libdmvae_hip_abl$n.so build/gemm_bf16_abl$n.o build/latent_abl$n.o \
-      build/gemm_bf16_256_abl$n.o build/gemm_f32.o build/latent_mfma.o build/latent_vade.o build/elementwise.o build/conv.o build/heads_dx_abl$n.o build/heads_latent_abl$n.o build/strip_fwd2.o build/api_abl$n.o
+      build/gemm_bf16_256_abl$n.o build/gemm_f32.o build/latent_mfma.o build/latent_vade.o build/latent_vade_mfma.o build/elementwise.o build/conv.o build/heads_dx_abl$n.o build/heads_latent_abl$n.o build/strip_fwd2.o build/api_abl$n.o
   echo build/libdmvae_hip_abl$n.so
 done
