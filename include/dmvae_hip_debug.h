@@ -5,7 +5,9 @@
  * bench.py's roofline leg uses dmvae_prof_* / dmvae_debug_spin; tools/ uses the probes and knobs; tests/test_gpu_conv_kernels.py
  * runs every kernel of the CNN trunk alone, on buffers of its own, through dmvae_debug_conv_* / _zero_border / _maxpool2_*;
  * tests/test_gpu_gemm_forms.py forces every tile form of the dense GEMMs through dmvae_debug_set_tile and knobs 0 / 1 / 7 / 9 (and 2 / 13 / 18),
- * checks with dmvae_prof_* which instantiation ran, and holds every fused epilogue on it to an exact reference.
+ * checks with dmvae_prof_* which instantiation ran, and holds every fused epilogue on it to an exact reference;
+ * tests/test_gpu_dw_adam_forms.py does the same for the fused weight-gradient + Adam epilogue (dmvae_gemm_grouped_dw_adam): knobs 2 and 6 (and 1)
+ * force each small tile and the 256x256 macro tile alone, dmvae_prof_* says which kernel families ran and how often.
  */
 #ifndef DMVAE_HIP_DEBUG_H
 #define DMVAE_HIP_DEBUG_H

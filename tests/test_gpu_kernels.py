@@ -16,6 +16,7 @@ import dmvae_oracle as O
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 
 import philox_oracle as PH      # noqa: E402
+import adam_exact as AX         # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -546,10 +547,13 @@ def test_adam_tf_matches_oracle_over_steps(hip, shadow, ieee):
     pd, md, vd = dev(p["a"]), torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
     pb = torch.zeros(n, dtype=torch.bfloat16, device="cuda") if shadow else None
     p32, m32, v32 = pd.clone(), md.clone(), vd.clone()          # the fp32 mode beside it: IEEE in bf16 mode must give ITS bits
+    exact = ieee or not shadow                                  # the two IEEE modes: the float32 oracle's bits (tests/helpers/adam_exact.py)
+    po, mo, vo = p["a"].astype(np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
     for t in range(1, 6):
         g = (rng.randn(n) * 10 ** rng.uniform(-4, 1)).astype(np.float32).astype(np.float64)
         gd = dev(g * 2.0)    # grad_scale 0.5 undoes the factor 2 (the 1/world path)
         O.adam_tf(p, {"a": g}, m, v, t, lr=0.002)
+        po, mo, vo = AX.adam_f32(po, mo, vo, (g * 2.0).astype(np.float32), 0.5, AX.lr_t(t))
         L.check(L.lib.dmvae_adam_tf(stream(), n, L.ptr(pd), L.ptr(gd), L.ptr(md), L.ptr(vd), L.ptr(pb) if shadow else None, 0.002, 0.9, 0.999,
                                     1e-8, 0.5, flags, t, None))
         if ieee:
@@ -561,6 +565,10 @@ def test_adam_tf_matches_oracle_over_steps(hip, shadow, ieee):
         np.testing.assert_allclose(md.cpu().numpy(), m["a"], rtol=1e-5, atol=2e-7)
         # (1 - beta2) is evaluated in float32, as TF's kernel does: 1.3e-5 relative to the double oracle
         np.testing.assert_allclose(vd.cpu().numpy(), v["a"], rtol=3e-5, atol=1e-12)
+        if exact:
+            for name, got, want in (("m", md, mo), ("v", vd, vo), ("param", pd, po)):
+                bad = got.cpu().numpy().view(np.uint32) != want.view(np.uint32)
+                assert not bad.any(), "t = %d: %d elements of %s are not the float32 oracle's bits" % (t, int(bad.sum()), name)
         assert not gd.any().item()                                   # zero_grad
         if shadow: np.testing.assert_array_equal(pb.float().cpu().numpy(), pd.to(torch.bfloat16).float().cpu().numpy())
     # step 1 from zero state ~ -lr*sign(g)
