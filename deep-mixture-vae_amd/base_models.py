@@ -392,6 +392,29 @@ class DeepMixtureVAE(VAE):
         _, _, logits = self.encode(data._rows[order])
         return get_clustering_accuracy(logits, data._cls[order])
 
+    def get_log_likelihood(self, session, data, k=50, counter=0):
+        """Held-out log-likelihood of `data` in nats per row: the importance-weighted bound (Burda et al., 2016) with k draws of Z per
+        row on the marginal mixture prior, computed on the GPU from the resident rows (StepEngine.eval_loglik; k = 1: an ELBO).  The
+        same formula for DeepMixtureVAE and VaDE.  Walks the data set in its current order, batch after batch as
+        get_accuracy(eval="device") does, WITHOUT reshuffling: nothing is drawn from the NumPy stream.  The noise is the device's
+        Philox stream 4 keyed by (seed, counter, draw, position of the row): two calls with one counter return the same bits.
+        The loop only enqueues; one float64 pair comes back at the end."""
+        import torch
+        eng, dev = self._engine, self._session.device
+        rows = data.device_rows(dev)
+        order = data.order
+        t = torch.as_tensor(np.ascontiguousarray(order, dtype=np.int32))
+        if self._eval_perm is None or self._eval_perm.numel() != t.numel():
+            self._eval_perm = torch.empty(t.numel(), dtype=torch.int32, device=dev)
+        self._eval_perm.copy_(t)
+        acc = eng.loglik_buffer()
+        b, N = eng.max_batch, len(order)
+        for s in range(0, N, b):
+            n = min(b, N - s)
+            eng.load_batch(rows, self._eval_perm, s, n)
+            eng.eval_loglik(acc, n, N, s, k, counter=counter)
+        return eng.read_loglik(acc)[0]
+
     # ------------------------------------------------------------------ pretraining (base_models.py:304-423)
     # the variables tf.get_collection(TRAINABLE_VARIABLES, scope=name + "/encoder_network/c") returns (:313-315)
     PRIOR_VAR_LIST = ("W_ch", "b_ch", "W_logits", "b_logits")

@@ -15,6 +15,7 @@
 #include "gmm_fit.h"
 #include "gmm_seed.h"
 #include "eval_clusters.h"
+#include "eval_loglik.h"
 #include "measure.h"
 
 namespace dmvae {
@@ -904,6 +905,56 @@ extern "C" int dmvae_plan_eval_clusters(dmvae_plan* p, void* stream, int n_valid
     TRY(vade_eval_check(a, "dmvae_plan_eval_clusters"));
     TRY(encode_impl(p, s));
     return vade_eval_launch(s, a);
+}
+
+// Held-out log-likelihood of the loaded batch (eval_loglik.hip): the importance-weighted bound with `draws` samples per row.  One encoder pass, then per
+// draw {z_s and log p(z_s) - log q_s, the decoder's hidden layers, the output layer's f32 logits into the "recon" buffer, the row sums and the running
+// logsumexp}, then the rows' L and their sum.  Reads parameters; writes activation views and the caller's scratch only: no gradient, no state change.
+extern "C" int64_t dmvae_plan_eval_loglik_ws_bytes(const dmvae_plan* p) { return p ? loglik_ws_bytes(p->Bp) : (int64_t)DMVAE_EINVAL; }
+
+extern "C" int dmvae_plan_eval_loglik(dmvae_plan* p, void* stream, int n_valid, int64_t n_rows, int64_t first, int draws, const float* eps, int64_t ld_eps,
+                                      uint64_t eval_counter, void* ws, int64_t ws_bytes, float* row_ll, double* acc) {
+    DMVAE_REQUIRE(p && p->bound, "dmvae_plan_eval_loglik: plan not bound");
+    DMVAE_REQUIRE(n_valid >= 0 && n_valid <= p->cfg.max_batch, "dmvae_plan_eval_loglik: n_valid=%d exceeds max_batch=%d", n_valid, p->cfg.max_batch);
+    DMVAE_REQUIRE(draws >= 1 && draws <= LOGLIK_MAX_DRAWS, "dmvae_plan_eval_loglik: draws=%d (1 .. %d)", draws, LOGLIK_MAX_DRAWS);
+    DMVAE_REQUIRE(first >= 0 && first + n_valid <= n_rows, "dmvae_plan_eval_loglik: rows [%lld, %lld + %d) are not inside the %lld rows of the data set",
+                  (long long)first, (long long)first, n_valid, (long long)n_rows);
+    DMVAE_REQUIRE(!eps || ld_eps >= p->cfg.latent_dim, "dmvae_plan_eval_loglik: ld_eps=%lld < latent_dim=%d", (long long)ld_eps, p->cfg.latent_dim);
+    const int64_t need = loglik_ws_bytes(p->Bp);
+    DMVAE_REQUIRE(ws && ws_bytes >= need && (uintptr_t)ws % 4 == 0, "dmvae_plan_eval_loglik: the scratch holds %lld bytes, %lld are needed (dmvae_plan_eval_loglik_ws_bytes)",
+                  (long long)(ws ? ws_bytes : 0), (long long)need);
+    DMVAE_REQUIRE(acc, "dmvae_plan_eval_loglik: null acc");
+    DMVAE_REQUIRE(!p->tsrc_valid, "dmvae_plan_eval_loglik: load the batch with dmvae_plan_load_batch (the f32 copy of the batch holds the targets)");
+    hipStream_t s = (hipStream_t)stream;
+    const dmvae_config& c = p->cfg;
+    float* a_s = reinterpret_cast<float*>(ws);
+    float* run_m = a_s + p->Bp;
+    float* run_s = run_m + p->Bp;
+    LoglikDrawArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_valid = n_valid; a.B_pad = p->Bp; a.D = c.latent_dim; a.K = c.n_classes; a.act_dtype = c.dtype;
+    a.n_rows = n_rows; a.first = first;
+    a.mean = reinterpret_cast<const float*>(WS(p, p->o_mv)); a.ld_mean = 2 * p->Dp;
+    a.log_var = a.mean + p->Dp; a.ld_log_var = 2 * p->Dp;
+    a.prior_means = p->buf.param + p->prior_off;
+    a.prior_log_vars = a.prior_means + (int64_t)c.n_classes * c.latent_dim;
+    a.eps = eps; a.ld_eps = ld_eps;
+    a.seed = c.seed; a.counter = eval_counter;
+    a.Z_act = WS(p, p->o_Z); a.ld_Z = p->Dp;
+    a.Z_f32 = c.dtype == DMVAE_BF16 ? reinterpret_cast<float*>(WS(p, p->o_Zf)) : nullptr; a.ld_Zf = p->Dp;
+    a.a_out = a_s;
+    if (n_valid == 0) return 0;
+    TRY(encode_impl(p, s));
+    const int last = (int)p->dec.size() - 1;
+    for (int d = 0; d < draws; ++d) {
+        a.draw = d;
+        TRY(loglik_draw_launch(s, a));
+        TRY(decode_hidden(p, s));
+        TRY(fwd_dense(p, s, WS(p, p->o_dec[last]), p->dec[last].out_pad, p->dec[last].out_pad, p->out, p->Ip, 0, DMVAE_EPI_BIAS_F32, WS(p, p->o_recon), p->Ip));
+        TRY(loglik_rows_launch(s, reinterpret_cast<const float*>(WS(p, p->o_recon)), reinterpret_cast<const float*>(WS(p, p->o_xf)), p->Ip, c.input_dim, n_valid,
+                               c.input_type, d, a_s, run_m, run_s));
+    }
+    return loglik_finish_launch(s, run_m, run_s, n_valid, draws, row_ll, acc);
 }
 
 // Split-K of the dW GEMMs: off.  Measured (tools/gemm_sweep.py) fp32-atomic split-K loses on every

@@ -41,6 +41,7 @@ EXPORTS = [
     "dmvae_gmm_ws_bytes", "dmvae_gmm_fit", "dmvae_gmm_kmeans",
     "dmvae_gmm_seed_ws_bytes", "dmvae_gmm_seed", "dmvae_philox_uniform",
     "dmvae_confusion_add", "dmvae_plan_eval_clusters",
+    "dmvae_plan_eval_loglik_ws_bytes", "dmvae_plan_eval_loglik",
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
     "dmvae_debug_conv_first_fwd", "dmvae_debug_conv_first_dw", "dmvae_debug_zero_border", "dmvae_debug_maxpool2_fwd", "dmvae_debug_maxpool2_bwd_relu",
     "dmvae_debug_conv_wflip", "dmvae_debug_conv_gemm", "dmvae_debug_conv_dw",
@@ -236,6 +237,8 @@ def _load():
         "dmvae_philox_uniform": [vp, vp, i64, u64, u64, u32],
         "dmvae_confusion_add": [vp, vp, i64, i32, i32, vp, i64, vp, i64, vp, i32, vp],
         "dmvae_plan_eval_clusters": [vp, vp, i32, vp, i64, vp, i64, i32, vp, i64, u64, vp, i32, vp],
+        "dmvae_plan_eval_loglik_ws_bytes": [vp],
+        "dmvae_plan_eval_loglik": [vp, vp, i32, i64, i64, i32, vp, i64, u64, vp, i64, vp, vp],
         "dmvae_prof_enable": [i32],
         "dmvae_debug_spin": [vp, i32],
         "dmvae_debug_strip_fwd2": [vp, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64],
@@ -266,6 +269,7 @@ def _load():
     lib.dmvae_heads_latent_kslice_floats.restype = C.c_int64
     lib.dmvae_gmm_ws_bytes.restype = C.c_int64
     lib.dmvae_gmm_seed_ws_bytes.restype = C.c_int64
+    lib.dmvae_plan_eval_loglik_ws_bytes.restype = C.c_int64
     lib.dmvae_plan_destroy.restype = None
     got = lib.dmvae_abi_version()
     if got != ABI_VERSION:       # the public structs grew between versions: a mismatched pair would read past them

@@ -634,6 +634,35 @@ class StepEngine:
                 m for bit, m in ((1, "a class outside [0, %d)" % R), (2, "a permutation entry outside the data set")) if host[-1] & bit))
         return host[:-1].reshape(R, R).astype(np.int64)
 
+    # ------------------------------------------------------------ held-out log-likelihood on the device
+    def loglik_buffer(self):
+        """a zeroed float64 [2] device buffer: [sum of the rows' log-likelihood bounds, rows] (eval_loglik adds into it)"""
+        return torch.zeros(2, dtype=torch.float64, device=self.device)
+
+    def eval_loglik(self, acc, n_valid, n_rows, first, draws, eps=None, counter=0, row_ll=None):
+        """dmvae_plan_eval_loglik on the batch load_batch assembled (rows first .. first + n_valid of the n_rows evaluated): one encoder
+        pass, then `draws` samples of Z through the decoder; the importance-weighted bound L of every row (row_ll: device f32
+        [>= n_valid], optional) and acc[0] += sum L, acc[1] += n_valid.  eps: f32 [draws, n_valid, latent_dim] on the device, or
+        None: Philox in the kernel, keyed by (seed, counter, draw, first + row).  Only enqueues: read_loglik() after the last batch
+        is the one synchronisation."""
+        n_valid, draws = int(n_valid), int(draws)
+        assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == 2, "acc: StepEngine.loglik_buffer()"
+        if eps is not None:
+            assert eps.dtype == torch.float32 and eps.is_contiguous() and eps.shape == (draws, n_valid, self.latent_dim)
+        if row_ll is not None:
+            assert row_ll.dtype == torch.float32 and row_ll.is_contiguous() and row_ll.numel() >= n_valid
+        ws = getattr(self, "_loglik_ws", None)
+        if ws is None:      # the caller's scratch of the C entry: kept with the engine, outside the plan's workspace
+            ws = self._loglik_ws = torch.empty(int(lib.dmvae_plan_eval_loglik_ws_bytes(self._plan)), dtype=torch.uint8, device=self.device)
+        check(lib.dmvae_plan_eval_loglik(self._plan, self._stream(), n_valid, int(n_rows), int(first), draws, ptr(eps), self.latent_dim,
+                                         int(counter) & 0xFFFFFFFFFFFFFFFF, ptr(ws), ws.numel(), ptr(row_ll), ptr(acc)), "dmvae_plan_eval_loglik")
+
+    @staticmethod
+    def read_loglik(acc):
+        """(mean log-likelihood bound in nats per row, rows) of everything added into acc: one synchronising copy"""
+        total, rows = acc.cpu().tolist()
+        return (total / rows if rows else float("nan")), int(rows)
+
     def decode(self, Z):
         assert Z.dtype == torch.float32 and Z.is_contiguous() and Z.shape[1] == self.latent_dim
         check(lib.dmvae_plan_decode(self._plan, self._stream(), ptr(Z), self.latent_dim, Z.shape[0]), "dmvae_plan_decode")

@@ -13,7 +13,8 @@ GMM-initialised prior tables, latent-loss Adam over the c-head).
 New flags (defaults = reference behaviour): --batch_size, --dtype, --seed,
 --host_noise, --gumbel, --temperature, --enc_layers, --head_dim, --dec_layers,
 --gmm, --gmm_seeding (host | device: where --gmm device draws its k-means++ centres),
---eval (host | device: where get_accuracy takes its arg-max and confusion matrix).
+--eval (host | device: where get_accuracy takes its arg-max and confusion matrix),
+--loglik S (dmvae / vade: held-out log-likelihood of the test set per epoch, the importance-weighted bound with S draws; 0 = off).
 """
 import argparse
 import json
@@ -85,6 +86,9 @@ parser.add_argument("--gmm_seeding", type=str, default="host", choices=["host", 
 parser.add_argument("--eval", type=str, default="host", choices=["host", "device"],
                     help="get_accuracy: arg-max and confusion matrix in NumPy from scores copied back per batch (the reference's way) or on the "
                          "device from the resident rows (one small matrix read back per call)")
+parser.add_argument("--loglik", type=int, default=0,
+                    help="dmvae / vade: S > 0 adds llTest to the epoch line -- the test set's log-likelihood in nats per row, the importance-weighted "
+                         "bound with S draws computed on the device (get_log_likelihood); 0 = off")
 parser.add_argument("--cnn", action="store_true", default=False,
                     help="the checked-in convolutional encoder trunk (base_models.py:156,176-216) instead of the MLP branch")
 
@@ -197,6 +201,7 @@ def main(argv):
             accTrain = model.get_accuracy(sess, train_data)
             accTest = model.get_accuracy(sess, test_data)
             eval_seconds = time.perf_counter() - t_eval
+            llTest = model.get_log_likelihood(sess, test_data, k=argv.loglik, counter=epoch) if argv.loglik > 0 else None
             improved = accTest > maxAcc
             if world > 1:
                 # the branch below holds a COLLECTIVE (sync_master): rank 0 decides and every rank follows.  Each rank scores the same
@@ -223,12 +228,17 @@ def main(argv):
                 rec = dict(epoch=epoch, **ep, images_per_sec=(ep.get("rows", 0) / sec if sec else None), train_seconds=sec,
                            acc_train=float(accTrain), acc_test=float(accTest), max_acc=float(max(maxAcc, accTest) if improved else maxAcc),
                            eval_seconds=eval_seconds, eval=argv.eval, world=world, batch_size=argv.batch_size, dtype=argv.dtype, model=model_str)
+                if llTest is not None:
+                    rec.update(ll_test=float(llTest), loglik_draws=argv.loglik)
                 with open(argv.model + "_metrics.jsonl", "a") as fl:
                     fl.write(json.dumps(rec) + "\n")
             if math.isnan(loss):
                 raise FloatingPointError("loss is NaN at epoch %d (the reference drops into pdb here, train.py:320-321)" % epoch)
-            bar.set_postfix({"loss": "%.4f" % loss, "accTrain": "%.4f" % accTrain, "accTest": "%.4f" % accTest,
-                             "maxAcc": "%.4f" % maxAcc, "accClusteringTest": "%.4f" % accTest})
+            postfix = {"loss": "%.4f" % loss, "accTrain": "%.4f" % accTrain, "accTest": "%.4f" % accTest,
+                       "maxAcc": "%.4f" % maxAcc, "accClusteringTest": "%.4f" % accTest}
+            if llTest is not None:
+                postfix["llTest"] = "%.4f" % llTest
+            bar.set_postfix(postfix)
     if plotting:                                                  # train.py:332-334
         visualization.mnist_sample_plot(model, sess)
         visualization.mnist_regeneration_plot(model, test_data, sess)

@@ -573,6 +573,30 @@ int dmvae_plan_eval_clusters(dmvae_plan* p, void* stream, int n_valid, const int
                              int64_t first, int draws, const float* eps, int64_t ld_eps, uint64_t eval_counter, int32_t* conf, int R,
                              int32_t* err_flag);
 
+/* ---- held-out log-likelihood on the device (csrc/eval_loglik.hip): the importance-weighted bound of Burda et al. (2016) ------
+ * For the batch loaded by dmvae_plan_load_batch (the f32 copy of the batch holds the targets: a dmvae_plan_load_batch_step batch is
+ * refused), row r, draws s < S = draws, prior tables mu, lambda [K][D] (the same formula on DMVAE and VaDE plans: both hold a uniform
+ * prior over the clusters):
+ *   z_s = mean + exp(log_var / 2) eps_s                      (ONE encoder pass; bf16 plans: the decoder reads z_s rounded to bf16, the
+ *                                                             prior and posterior terms the f32 z_s, as in the step)
+ *   log q_s    = -1/2 sum_d (eps_sd^2 + log_var_d + log 2 pi)
+ *   log p(z_s) = logsumexp_k [ -1/2 sum_d ((z_sd - mu_kd)^2 exp(-lambda_kd) + lambda_kd + log 2 pi) ] - log K
+ *   log p(x | z_s), l = the decoder's logits of z_s:  binary  sum_{i < input_dim} (x_i l_i - max(l_i, 0) - log(1 + exp(-|l_i|)))
+ *                                                     real    -1/2 sum_{i < input_dim} (x_i - l_i)^2 - input_dim / 2 log 2 pi
+ *   w_s = log p(x | z_s) + log p(z_s) - log q_s,    L_r = logsumexp_s w_s - log S      (S = 1: an ELBO on the marginal mixture prior)
+ * row_ll (device f32 [n_valid], may be NULL) receives L_r; acc (device double [2], ADDED INTO: the caller zeroes it once, runs every
+ * batch of the set, reads it back once) gains sum_r L_r and n_valid.  No float atomics, fixed-order sums: two runs agree bit for bit.
+ * eps: device f32 [draws][n_valid][ld_eps], or NULL: Philox in the kernel, eps_s[r][d] = element ((s * n_rows + first + r) * latent_dim + d)
+ * of the stream (plan seed, step = eval_counter, stream id 4) of dmvae_philox_normal -- a function of the row's position in the
+ * evaluated order, not of the batch size.  ws: the caller's scratch of dmvae_plan_eval_loglik_ws_bytes() bytes (host arithmetic on
+ * batch_pad; the plan's own workspace does not grow).  Parameters, gradients, Adam moments and the step state are not written; the
+ * "Z", "recon" (left holding the last draw's f32 logits) and decoder activation views are.  The prior tables pass through LDS in tiles: every K and latent_dim a plan can be
+ * created with runs.  Every argument is checked before anything is enqueued; DMVAE_EINVAL: draws outside 1 .. 1024, first < 0,
+ * first + n_valid > n_rows, n_valid > max_batch, ld_eps < latent_dim, a scratch too small, acc NULL. */
+int64_t dmvae_plan_eval_loglik_ws_bytes(const dmvae_plan* p);
+int dmvae_plan_eval_loglik(dmvae_plan* p, void* stream, int n_valid, int64_t n_rows, int64_t first, int draws, const float* eps,
+                           int64_t ld_eps, uint64_t eval_counter, void* ws, int64_t ws_bytes, float* row_ll, double* acc);
+
 /* Measurement and tuning entry points (per-kernel timing for bench.py's roofline leg, probes, tile knobs) are
  * declared in dmvae_hip_debug.h: exported by the same library, not part of the drop-in boundary. */
 int dmvae_abi_version(void);
