@@ -16,6 +16,7 @@
 #include "gmm_seed.h"
 #include "eval_clusters.h"
 #include "eval_loglik.h"
+#include "tsne.h"
 #include "measure.h"
 
 namespace dmvae {
@@ -1565,6 +1566,26 @@ extern "C" int dmvae_gmm_seed(void* stream, const dmvae_gmm_seed_config* cfg, co
                               float* centers, int32_t* rows) {
     return gmm_seed_launch((hipStream_t)stream, cfg, X, ldx, u, ws, ws_bytes, centers, rows);
 }
+extern "C" int64_t dmvae_tsne_ws_bytes(const dmvae_tsne_config* cfg) {
+    if (int rc = tsne_check(cfg, "dmvae_tsne_ws_bytes")) return rc;
+    return tsne_ws_bytes(cfg);
+}
+extern "C" int dmvae_tsne_joint_p(void* stream, const dmvae_tsne_config* cfg, const float* X, int64_t ldx, void* ws, int64_t ws_bytes, float* beta) {
+    return tsne_joint_p_launch((hipStream_t)stream, cfg, X, ldx, ws, ws_bytes, beta);
+}
+extern "C" int dmvae_tsne_gradient(void* stream, const dmvae_tsne_config* cfg, void* ws, int64_t ws_bytes, const float* Y, float exaggeration,
+                                   float* grad) {
+    return tsne_gradient_launch((hipStream_t)stream, cfg, ws, ws_bytes, Y, exaggeration, grad);
+}
+extern "C" int dmvae_tsne_step(void* stream, const dmvae_tsne_config* cfg, void* ws, int64_t ws_bytes, float* Y, float* U, float* G, float exaggeration,
+                               float momentum) {
+    return tsne_step_launch((hipStream_t)stream, cfg, ws, ws_bytes, Y, U, G, exaggeration, momentum);
+}
+extern "C" int dmvae_tsne_fit(void* stream, const dmvae_tsne_config* cfg, const float* X, int64_t ldx, const float* Y0, void* ws, int64_t ws_bytes,
+                              float* Y, double* kl) {
+    return tsne_fit_launch((hipStream_t)stream, cfg, X, ldx, Y0, ws, ws_bytes, Y, kl);
+}
+extern "C" const float* dmvae_tsne_p(const void* ws) { return (const float*)ws; }
 extern "C" int dmvae_confusion_add(void* stream, const float* scores, int64_t ld, int n_valid, int K, const int32_t* classes, int64_t n_rows,
                                    const int32_t* perm, int64_t first, int32_t* conf, int R, int32_t* err_flag) {
     return confusion_add_launch((hipStream_t)stream, scores, ld, K, EvalRows{classes, n_rows, perm, first, n_valid, conf, R, err_flag});

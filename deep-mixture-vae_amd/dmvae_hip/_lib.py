@@ -42,6 +42,7 @@ EXPORTS = [
     "dmvae_gmm_seed_ws_bytes", "dmvae_gmm_seed", "dmvae_philox_uniform",
     "dmvae_confusion_add", "dmvae_plan_eval_clusters",
     "dmvae_plan_eval_loglik_ws_bytes", "dmvae_plan_eval_loglik",
+    "dmvae_tsne_ws_bytes", "dmvae_tsne_joint_p", "dmvae_tsne_gradient", "dmvae_tsne_step", "dmvae_tsne_fit", "dmvae_tsne_p",
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
     "dmvae_debug_conv_first_fwd", "dmvae_debug_conv_first_dw", "dmvae_debug_zero_border", "dmvae_debug_maxpool2_fwd", "dmvae_debug_maxpool2_bwd_relu",
     "dmvae_debug_conv_wflip", "dmvae_debug_conv_gemm", "dmvae_debug_conv_dw",
@@ -65,6 +66,12 @@ class GmmResult(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "weights", "means", "covariances", "lower_bound", "n_iter", "converged", "best_restart", "lower_bounds", "n_iters",
         "convergeds", "all_weights", "all_means", "all_covariances", "centers", "labels", "kmeans_iters")]
+
+
+class TsneConfig(C.Structure):
+    """dmvae_tsne_config"""
+    _fields_ = [("N", C.c_int32), ("D", C.c_int32), ("perplexity", C.c_float), ("early_exaggeration", C.c_float), ("learning_rate", C.c_float),
+                ("n_iter", C.c_int32), ("exaggeration_iters", C.c_int32), ("seed", C.c_uint64), ("flags", C.c_int32)]
 
 
 class GmmSeedConfig(C.Structure):
@@ -239,6 +246,12 @@ def _load():
         "dmvae_plan_eval_clusters": [vp, vp, i32, vp, i64, vp, i64, i32, vp, i64, u64, vp, i32, vp],
         "dmvae_plan_eval_loglik_ws_bytes": [vp],
         "dmvae_plan_eval_loglik": [vp, vp, i32, i64, i64, i32, vp, i64, u64, vp, i64, vp, vp],
+        "dmvae_tsne_ws_bytes": [P(TsneConfig)],
+        "dmvae_tsne_joint_p": [vp, P(TsneConfig), vp, i64, vp, i64, vp],
+        "dmvae_tsne_gradient": [vp, P(TsneConfig), vp, i64, vp, f32, vp],
+        "dmvae_tsne_step": [vp, P(TsneConfig), vp, i64, vp, vp, vp, f32, f32],
+        "dmvae_tsne_fit": [vp, P(TsneConfig), vp, i64, vp, vp, i64, vp, vp],
+        "dmvae_tsne_p": [vp],
         "dmvae_prof_enable": [i32],
         "dmvae_debug_spin": [vp, i32],
         "dmvae_debug_strip_fwd2": [vp, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64],
@@ -270,6 +283,8 @@ def _load():
     lib.dmvae_gmm_ws_bytes.restype = C.c_int64
     lib.dmvae_gmm_seed_ws_bytes.restype = C.c_int64
     lib.dmvae_plan_eval_loglik_ws_bytes.restype = C.c_int64
+    lib.dmvae_tsne_ws_bytes.restype = C.c_int64
+    lib.dmvae_tsne_p.restype = C.c_void_p
     lib.dmvae_plan_destroy.restype = None
     got = lib.dmvae_abi_version()
     if got != ABI_VERSION:       # the public structs grew between versions: a mismatched pair would read past them

@@ -10,7 +10,9 @@ What a "reconstruction" and a "sample" are is taken from the reference:
 The figures are written as plain 8-bit greyscale PNGs (own zlib writer: the
 pixel grids are the product, no plotting library is needed on the GPU box) to
 the reference's paths plots/<model.name>/mnist/{regenerated,sampled}.png; the
-grids are also returned.  tsne=True adds the t-SNE scatter of the prior samples (:93-110) as an RGB panel.
+grids are also returned.  tsne=True adds the t-SNE scatter of the prior samples (:93-110) as an RGB panel;
+tsne_backend="host" embeds them with sklearn on the CPU (the reference's call), "device" with dmvae_hip.tsne.TSNE
+(exact t-SNE in HIP).
 """
 import os
 import struct
@@ -73,12 +75,18 @@ _COLORS = np.array([[31, 119, 180], [255, 127, 14], [44, 160, 44], [214, 39, 40]
                     [227, 119, 194], [127, 127, 127], [188, 189, 34], [23, 190, 207]], dtype=np.float64)
 
 
-def cluster_scatter(sample_Z, side=280):
+def cluster_scatter(sample_Z, side=280, tsne="host", seed=0):
     """visualization.py:93-110: the per-cluster prior samples (1000 each) reduced to two dimensions by t-SNE when the
-    latent space has more than two, drawn as one dot per sample coloured by cluster (colors[k % 10]) -> [side, side, 3]."""
+    latent space has more than two, drawn as one dot per sample coloured by cluster (colors[k % 10]) -> [side, side, 3].
+    tsne: "host" sklearn's TSNE on the CPU, "device" dmvae_hip.tsne.TSNE (seed: its random_state)."""
+    if tsne not in ("host", "device"):
+        raise ValueError("tsne must be 'host' or 'device'")
     Z = np.concatenate(sample_Z, axis=0)
     n_per = len(sample_Z[0])
-    if Z.shape[1] > 2:
+    if Z.shape[1] > 2 and tsne == "device":
+        from dmvae_hip import tsne as device_tsne
+        Z = np.asarray(device_tsne.TSNE(n_components=2, random_state=seed).fit_transform(Z), dtype=np.float64)
+    elif Z.shape[1] > 2:
         from sklearn.manifold import TSNE
         Z = TSNE(n_components=2).fit_transform(Z)
     lo, hi = Z.min(0), Z.max(0)
@@ -90,7 +98,7 @@ def cluster_scatter(sample_Z, side=280):
     return img
 
 
-def mnist_sample_plot(model, sess=None, tsne=False):
+def mnist_sample_plot(model, sess=None, tsne=False, tsne_backend="host"):
     sample_Z, decoded = sample_clusters(model, sess)
     side = int(round(np.sqrt(decoded[0].shape[1])))
     figure = np.zeros((side * model.n_classes, side * 10))
@@ -100,7 +108,7 @@ def mnist_sample_plot(model, sess=None, tsne=False):
             figure[i * side:(i + 1) * side, j * side:(j + 1) * side] = decoded[i][(10 * i + j) % 100].reshape(side, side) * 255
     if tsne:      # the sample grid on the left, the scatter of the prior samples on the right (visualization.py:93-110)
         h = figure.shape[0]
-        sc = cluster_scatter(sample_Z, side=h)
+        sc = cluster_scatter(sample_Z, side=h, tsne=tsne_backend)
         rgb = np.repeat(figure[:, :, None], 3, axis=2)
         _write_png("plots/%s/mnist/sampled.png" % model.name, np.concatenate([rgb, np.full((h, 14, 3), 255.0), sc], axis=1))
         return figure

@@ -14,7 +14,9 @@ New flags (defaults = reference behaviour): --batch_size, --dtype, --seed,
 --host_noise, --gumbel, --temperature, --enc_layers, --head_dim, --dec_layers,
 --gmm, --gmm_seeding (host | device: where --gmm device draws its k-means++ centres),
 --eval (host | device: where get_accuracy takes its arg-max and confusion matrix),
---loglik S (dmvae / vade: held-out log-likelihood of the test set per epoch, the importance-weighted bound with S draws; 0 = off).
+--loglik S (dmvae / vade: held-out log-likelihood of the test set per epoch, the importance-weighted bound with S draws; 0 = off),
+--tsne (off | host | device: with --plotting, sampled.png gains the t-SNE scatter of the prior samples, embedded by sklearn on the CPU or by
+the exact t-SNE in HIP, dmvae_hip.tsne.TSNE).
 """
 import argparse
 import json
@@ -89,6 +91,9 @@ parser.add_argument("--eval", type=str, default="host", choices=["host", "device
 parser.add_argument("--loglik", type=int, default=0,
                     help="dmvae / vade: S > 0 adds llTest to the epoch line -- the test set's log-likelihood in nats per row, the importance-weighted "
                          "bound with S draws computed on the device (get_log_likelihood); 0 = off")
+parser.add_argument("--tsne", type=str, default="off", choices=["off", "host", "device"],
+                    help="--plotting: add the t-SNE scatter of the prior samples (1000 per cluster) to sampled.png, embedded with sklearn on the "
+                         "host (the reference's call) or with the exact t-SNE on the device (dmvae_hip.tsne.TSNE); off = the sample grid alone")
 parser.add_argument("--cnn", action="store_true", default=False,
                     help="the checked-in convolutional encoder trunk (base_models.py:156,176-216) instead of the MLP branch")
 
@@ -192,7 +197,7 @@ def main(argv):
             if epoch % argv.save_epochs == 0 and argv.debug:
                 model.debug(sess, train_data)
             if plotting and epoch % argv.plot_epochs == 0:      # train.py:281-286
-                visualization.mnist_sample_plot(model, sess)
+                visualization.mnist_sample_plot(model, sess, tsne=argv.tsne != "off", tsne_backend=argv.tsne if argv.tsne != "off" else "host")
                 visualization.mnist_regeneration_plot(model, test_data, sess)
             if argv.kl_annealing and (epoch + 1) % argv.anneal_epochs == 0:
                 anneal_term = min(anneal_term + argv.anneal_step, 1.0)
@@ -240,7 +245,7 @@ def main(argv):
                 postfix["llTest"] = "%.4f" % llTest
             bar.set_postfix(postfix)
     if plotting:                                                  # train.py:332-334
-        visualization.mnist_sample_plot(model, sess)
+        visualization.mnist_sample_plot(model, sess, tsne=argv.tsne != "off", tsne_backend=argv.tsne if argv.tsne != "off" else "host")
         visualization.mnist_regeneration_plot(model, test_data, sess)
     if rank == 0:
         with open(argv.model + "_logs.txt", "a+") as fl:

@@ -597,6 +597,51 @@ int64_t dmvae_plan_eval_loglik_ws_bytes(const dmvae_plan* p);
 int dmvae_plan_eval_loglik(dmvae_plan* p, void* stream, int n_valid, int64_t n_rows, int64_t first, int draws, const float* eps,
                            int64_t ld_eps, uint64_t eval_counter, void* ws, int64_t ws_bytes, float* row_ll, double* acc);
 
+/* ---- exact t-SNE of latent samples on the device (csrc/tsne.hip; the scatter of visualization.py:93-110, which the reference draws with
+ * sklearn.manifold.TSNE(n_components=2)): sklearn's method="exact" with alpha = 1 and two output dimensions -------------------------
+ * X [N][ldx] f32, D columns.
+ *   d2_ij   = sum_d (x_id - x_jd)^2                      f32 differences, summed over d ascending (no norm expansion)
+ *   p_{j|i} = exp(-beta_i d'_j) / s_i,  d'_j = d2_ij - min_{j != i} d2_ij,  s_i = sum_{j != i} exp(-beta_i d'_j),  p_{i|i} = 0
+ *             beta_i: from 1, EXACTLY 64 bisection steps on H = log s + beta sum_j d'_j exp(-beta d'_j) / s against log(perplexity)
+ *             (H > log u: lo = beta, beta doubles while no upper bound is known, else (beta + hi) / 2; otherwise hi = beta,
+ *             beta = (beta + lo) / 2 with lo = 0 at first); s and the numerator are summed in f64.  No early exit: sklearn's search
+ *             stops at |H - log u| <= 1e-5 within 100 steps, this one is a function of the data alone.
+ *   P_ij    = (p_{j|i} + p_{i|j}) / 2N                   formed once per unordered pair: P == P^T bit for bit, zero diagonal, no floors
+ *   gradient at Y [N][2] with exaggeration e:  q_ij = 1 / (1 + |y_i - y_j|^2), q_ii = 0, Z = sum_ij q_ij (f64, rows in a fixed order),
+ *             g_i = 4 [ e sum_j P_ij q_ij (y_i - y_j) - (1 / Z) sum_j q_ij^2 (y_i - y_j) ]
+ *   step (sklearn's _gradient_descent, elementwise): inc = U g < 0; G = inc ? G + 0.2 : 0.8 G; G = max(G, 0.01);
+ *             U = momentum U - learning_rate (G g); Y += U
+ *   fit:      joint P; Y = Y0, or Y0 == NULL: Y[k] = 1e-4f * element k (k < 2N) of the Philox stream (seed, step 0, stream id 5) of
+ *             dmvae_philox_normal; U = 0, G = 1; n_iter steps -- the first exaggeration_iters with e = early_exaggeration and
+ *             momentum 0.5, the others with e = 1 and momentum 0.8 -- and KL = sum_{P_ij > 0} P_ij log(P_ij Z / q_ij) in f64 at the
+ *             final Y.  ALL n_iter steps run: sklearn's n_iter_without_progress / min_grad_norm checks are left out.
+ * dmvae_tsne_fit is dmvae_tsne_joint_p, then n_iter times what dmvae_tsne_step enqueues, then the KL: the same bits.
+ * The workspace holds the dense [N][N] f32 matrix first (d2, then p_{j|i}, then P, in place: dmvae_tsne_p(ws) == ws) and O(N) behind
+ * it; it must be 16-byte aligned, Y / U / G / grad / kl 8-byte aligned.  dmvae_tsne_gradient and dmvae_tsne_step need the P that
+ * dmvae_tsne_joint_p left in the same workspace for the same config.  beta (device f32 [N], may be NULL) receives the beta_i.
+ * No float atomics, fixed-order sums: two runs agree bit for bit.  The calls enqueue only -- 3 launches for the joint P, 3 per
+ * step, 4 for the KL -- and never synchronise.  Every argument is checked before anything is enqueued; DMVAE_EINVAL: N < 4, D < 1,
+ * perplexity outside (1, N - 1), n_iter or exaggeration_iters < 0, early_exaggeration or learning_rate not > 0, flags != 0, ldx < D,
+ * a workspace too small or misaligned, a null pointer.  DMVAE_EUNSUPPORTED: N > 32768 (the matrix would pass 4 GiB). */
+typedef struct dmvae_tsne_config {
+    int32_t N, D;
+    float perplexity;
+    float early_exaggeration;
+    float learning_rate;
+    int32_t n_iter;
+    int32_t exaggeration_iters;
+    uint64_t seed;           /* of the Philox stream when Y0 is NULL                */
+    int32_t flags;           /* reserved: 0                                         */
+} dmvae_tsne_config;
+int64_t dmvae_tsne_ws_bytes(const dmvae_tsne_config* cfg);      /* < 0: an error code */
+int dmvae_tsne_joint_p(void* stream, const dmvae_tsne_config* cfg, const float* X, int64_t ldx, void* ws, int64_t ws_bytes, float* beta);
+int dmvae_tsne_gradient(void* stream, const dmvae_tsne_config* cfg, void* ws, int64_t ws_bytes, const float* Y, float exaggeration, float* grad);
+int dmvae_tsne_step(void* stream, const dmvae_tsne_config* cfg, void* ws, int64_t ws_bytes, float* Y, float* U, float* G, float exaggeration,
+                    float momentum);
+int dmvae_tsne_fit(void* stream, const dmvae_tsne_config* cfg, const float* X, int64_t ldx, const float* Y0, void* ws, int64_t ws_bytes, float* Y,
+                   double* kl);
+const float* dmvae_tsne_p(const void* ws);
+
 /* Measurement and tuning entry points (per-kernel timing for bench.py's roofline leg, probes, tile knobs) are
  * declared in dmvae_hip_debug.h: exported by the same library, not part of the drop-in boundary. */
 int dmvae_abi_version(void);
