@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void latent_pre_kernel(LatentMfmaArgs L, int n
     const dmvae_latent_args& a = L.a;
     if ((int)blockIdx.x >= nrow_blocks) {        // extra workgroups: the prior tables as GEMM operands
         __shared__ float tred[8];
-        latent_tables_block((int)blockIdx.x - nrow_blocks, a.prior_means, a.prior_log_vars, a.K, a.D, L.w.Kp, L.w.Dp, L.ws + L.w.T1, L.ws + L.w.T2,
+        latent_tables_block((int)blockIdx.x - nrow_blocks, a.prior_means, a.prior_log_vars, nullptr, a.K, a.D, L.w.Kp, L.w.Dp, L.ws + L.w.T1, L.ws + L.w.T2,
                             L.ws + L.w.c2, L.ws + L.w.ck, tred);
         return;
     }

@@ -11,7 +11,8 @@ static inline int pad64i(int x) { return (x + 63) / 64 * 64; }
 
 // ---- prior tables -> GEMM operands (tiny: K * D elements)
 //   T1 = [ip | pm ip],  T2 = [ip | -2 pm ip]  ([Kp][2 Dp], pad rows / columns zero),  c2_k = sum_d pm^2 ip,  ck_k = sum_d plv
-__device__ __forceinline__ void latent_tables_block(const int k, const float* __restrict__ pm, const float* __restrict__ plv, int K, int D, int Kp, int Dp,
+//   m0 (nullptr: none): the origin [Dp] the means are taken from, pm - m0 in every product (latent_vade_mfma.hip: vade_origin_kernel)
+__device__ __forceinline__ void latent_tables_block(const int k, const float* __restrict__ pm, const float* __restrict__ plv, const float* __restrict__ m0, int K, int D, int Kp, int Dp,
                                                     float* __restrict__ T1, float* __restrict__ T2, float* __restrict__ c2, float* __restrict__ ck, float* red) {
     // one block per (padded) cluster row k
     float s2 = 0.f, sl = 0.f;
@@ -20,6 +21,7 @@ __device__ __forceinline__ void latent_tables_block(const int k, const float* __
         if (k < K && d < D) {
             const float lv = plv[(int64_t)k * D + d];
             m = pm[(int64_t)k * D + d];
+            if (m0) m -= m0[d];
             ip = __expf(-lv);
             s2 += m * m * ip;
             sl += lv;

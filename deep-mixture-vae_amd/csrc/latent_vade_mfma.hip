@@ -17,6 +17,8 @@
 //         -> d pm  = -r/B ip (Gg_mu - pm Wsum) + ip (Gu_z - pm Usum)
 //            d plv = r/2B (Wsum - ip (Gg_e - 2 pm Gg_mu + pm^2 Wsum)) + 1/2 (ip (Gu_zz - 2 pm Gu_z + pm^2 Usum) - Usum)
 //
+// mu, z and pm above are all taken from one origin m0 (vade_origin_kernel: only differences enter the stage; the expansion is what the
+// shift is for); Z as the caller sees it is not shifted.
 // (oracle/dmvae_oracle.py::vade_latent_backward with the squares expanded; tests/test_vade_large_host.py holds the algebra.)
 // Launches: vade_pre (+ the tables as extra workgroups), G2, vade_rows, G1 + G3 as one grid, vade_post (+ the prior-table
 // gradients as extra workgroups).  The expanded squares cancel: bf16 operands are not an option (latent_mfma.hip).  The
@@ -39,7 +41,7 @@ namespace dmvae {
 
 struct VadeMfmaWs {        // float offsets into the caller's scratch
     int Dp, Kp, XW, nsplit, nsplit_s;      // K slices of each half of G3 (over the batch) and of G2 (over 2D)
-    int64_t T1, T2, c2, ck, X, S, RL, W2, AC, G, total;
+    int64_t T1, T2, c2, ck, X, S, RL, W2, AC, G, m0, total;
 };
 static VadeMfmaWs vade_mfma_layout(int Bp, int D, int K) {
     VadeMfmaWs w;
@@ -60,6 +62,7 @@ static VadeMfmaWs vade_mfma_layout(int Bp, int D, int K) {
     w.X = take((int64_t)2 * Bp * w.XW); w.S = take((int64_t)nss * 2 * Bp * w.Kp); w.RL = take(Bp);
     w.W2 = take((int64_t)2 * Bp * w.Kp); w.AC = take((int64_t)2 * Bp * 2 * w.Dp);
     w.G = take((int64_t)2 * ns * w.Kp * w.XW);
+    w.m0 = take(w.Dp);
     w.total = o;
     return w;
 }
@@ -80,9 +83,33 @@ struct VadeMfmaArgs {
     float* ws;
 };
 
+// The origin of every expanded product: m0_d = sum_k w_kd pm_kd / sum_k w_kd with w = ip^2 (taken relative to the dimension's largest, so
+// that it cannot overflow) -- the point that makes the GEMM operand column (pm - m0) ip smallest in the least-squares sense.  The stage is
+// invariant under a common shift of mean, z and the prior means (only differences enter it), but the expanded squares are not: with pm ~ 1
+// and ip = 1e6 (a cluster collapsed onto the reg_covar floor, a dead latent dimension) z^2 ip - 2 z pm ip + pm^2 ip cancels 2.5e8 down
+// to D at D = 256 and the scores of the rows ON that cluster were off by tens of nats; from m0 that cluster's pm is ~ 0 and its rows' z is
+// a small DIFFERENCE taken first.  One thread per dimension, clusters in ascending order: every launch computes the same bits.
+__global__ __launch_bounds__(256) void vade_origin_kernel(const float* __restrict__ pm, const float* __restrict__ plv, int K, int D, int Dp, float* __restrict__ m0) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= Dp) return;
+    float v = 0.f;
+    if (d < D) {
+        float mn = INFINITY;
+        for (int k = 0; k < K; ++k) mn = fminf(mn, plv[(int64_t)k * D + d]);
+        float s1 = 0.f, s2 = 0.f;
+        for (int k = 0; k < K; ++k) {
+            const float wk = __expf(2.f * (mn - plv[(int64_t)k * D + d]));
+            s1 += wk * pm[(int64_t)k * D + d];
+            s2 += wk;
+        }
+        v = s1 / s2;
+    }
+    m0[d] = v;
+}
+
 __global__ __launch_bounds__(256) void vade_tables_kernel(const float* pm, const float* plv, int K, int D, VadeMfmaWs w, float* ws) {
     __shared__ float tred[8];
-    latent_tables_block((int)blockIdx.x, pm, plv, K, D, w.Kp, w.Dp, ws + w.T1, ws + w.T2, ws + w.c2, ws + w.ck, tred);
+    latent_tables_block((int)blockIdx.x, pm, plv, ws + w.m0, K, D, w.Kp, w.Dp, ws + w.T1, ws + w.T2, ws + w.c2, ws + w.ck, tred);
 }
 
 // ---- rows, before the GEMMs.  16 lanes per row, 16 rows per 256-thread block; a lane owns quads of columns.
@@ -90,7 +117,7 @@ __global__ __launch_bounds__(256) void vade_pre_kernel(VadeMfmaArgs L, int nrow_
     const dmvae_latent_args& a = L.a;
     if ((int)blockIdx.x >= nrow_blocks) {        // extra workgroups: the prior tables as GEMM operands
         __shared__ float tred[8];
-        latent_tables_block((int)blockIdx.x - nrow_blocks, a.prior_means, a.prior_log_vars, a.K, a.D, L.w.Kp, L.w.Dp, L.ws + L.w.T1, L.ws + L.w.T2,
+        latent_tables_block((int)blockIdx.x - nrow_blocks, a.prior_means, a.prior_log_vars, L.ws + L.w.m0, a.K, a.D, L.w.Kp, L.w.Dp, L.ws + L.w.T1, L.ws + L.w.T2,
                             L.ws + L.w.c2, L.ws + L.w.ck, tred);
         return;
     }
@@ -129,21 +156,24 @@ __global__ __launch_bounds__(256) void vade_pre_kernel(VadeMfmaArgs L, int nrow_
             }
         }
         if (valid && d0 < D && !a.eps) philox_normal4(a.seed, nstep, 0u, (uint64_t)b * (Dp / 4) + q4, ep);
-        float z[4], cl[4], x1[4];
+        const float4 o4 = *reinterpret_cast<const float4*>(L.ws + L.w.m0 + d0);      // the origin of the GEMM operands (vade_origin_kernel); Z itself is not shifted
+        const float org[4] = {o4.x, o4.y, o4.z, o4.w};
+        float z[4], cl[4], x1[4], zs[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const bool ok = valid && d0 + j < D;
             const float e = __expf(lv[j]), sd = __expf(0.5f * lv[j]);
             z[j] = ok ? mu[j] + sd * ep[j] : 0.f;
             cl[j] = ok ? ep[j] * 0.5f * sd : 0.f;
+            mu[j] = ok ? mu[j] - org[j] : 0.f;
+            zs[j] = ok ? z[j] - org[j] : 0.f;
             x1[j] = ok ? e + mu[j] * mu[j] : 0.f;
-            mu[j] = ok ? mu[j] : 0.f;
             lvsum += ok ? lv[j] : 0.f;
         }
         *reinterpret_cast<float4*>(Xm + d0) = make_float4(x1[0], x1[1], x1[2], x1[3]);
         *reinterpret_cast<float4*>(Xm + Dp + d0) = make_float4(mu[0], mu[1], mu[2], mu[3]);
-        *reinterpret_cast<float4*>(Xz + d0) = make_float4(z[0] * z[0], z[1] * z[1], z[2] * z[2], z[3] * z[3]);
-        *reinterpret_cast<float4*>(Xz + Dp + d0) = make_float4(z[0], z[1], z[2], z[3]);
+        *reinterpret_cast<float4*>(Xz + d0) = make_float4(zs[0] * zs[0], zs[1] * zs[1], zs[2] * zs[2], zs[3] * zs[3]);
+        *reinterpret_cast<float4*>(Xz + Dp + d0) = make_float4(zs[0], zs[1], zs[2], zs[3]);
         // outputs: Z (act dtype, pad columns up to ld_Z zeroed: they are K padding of the first decoder GEMM), f32 copy, coefficient
         if (vec && d0 + 4 <= a.ld_Z) {
             if (a.act_dtype == DMVAE_BF16) {
@@ -324,7 +354,7 @@ __global__ __launch_bounds__(256) void vade_post_kernel(VadeMfmaArgs L, int nrow
                 gzz += g[d]; gz += g[Dp + d]; usum += g[2 * Dp];
             }
             const float ip = L.ws[L.w.T1 + (int64_t)k * 2 * Dp + d];
-            const float pmv = a.prior_means[idx];
+            const float pmv = a.prior_means[idx] - L.ws[L.w.m0 + d];      // (the tables' origin: G holds sums of the shifted mean and z)
             a.dprior_partials[idx] = -rB * ip * (gm - pmv * wsum) + ip * (gz - pmv * usum);
             a.dprior_partials[KD + idx] = rB2 * (wsum - ip * (ge - 2.f * pmv * gm + pmv * pmv * wsum)) +
                                           0.5f * (ip * (gzz - 2.f * pmv * gz + pmv * pmv * usum) - usum);
@@ -399,11 +429,17 @@ int latent_vade_mfma_launch(hipStream_t s, const dmvae_latent_args* a, float* ws
     L.a = *a; L.w = w; L.ws = ws;
     const int nrb = a->B_pad / 16, Bp2 = 2 * a->B_pad;
     const double BD = (double)a->B * a->D, BK = (double)a->B * a->K;
+    {
+        ProfScope ps(s, "vade_origin", 0.0, 16.0 * a->K * a->D);
+        DMVAE_LAUNCH(vade_origin_kernel, dim3((w.Dp + 255) / 256), dim3(256), 0, s, a->prior_means, a->prior_log_vars, a->K, a->D, w.Dp, ws + w.m0);
+    }
+    int rc = check_launch("vade_origin");
+    if (rc) return rc;
     {   // the prior-table operands ride as Kp extra workgroups of the row kernel
         ProfScope ps(s, "vade_pre", 0.0, 4.0 * (BD * (2.0 + (a->eps ? 1.0 : 0.0) + 4.0 + 2.0 + 1.0)) + 16.0 * a->K * a->D);
         DMVAE_LAUNCH(vade_pre_kernel, dim3(nrb + w.Kp), dim3(256), 0, s, L, nrb);
     }
-    int rc = check_launch("vade_pre");
+    rc = check_launch("vade_pre");
     if (rc) return rc;
     {
         ProfScope ps(s, "vade_gemm_f32", 2.0 * Bp2 * (double)w.Kp * 2.0 * w.Dp, 4.0 * Bp2 * (2.0 * w.Dp + (double)w.nsplit_s * w.Kp));
@@ -480,7 +516,7 @@ __global__ __launch_bounds__(256) void vade_eval_z_kernel(VadeEvalMfma L, int j)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (!erow) ep[i] = philox_normal_at(a.seed, a.counter, EVAL_PHILOX_STREAM, ((uint64_t)j * (uint64_t)a.rows.n_rows + pos) * (uint64_t)D + (d0 + i < D ? d0 + i : 0));
-                z[i] = d0 + i < D ? mu[i] + __expf(0.5f * lv[i]) * ep[i] : 0.f;
+                z[i] = d0 + i < D ? mu[i] + __expf(0.5f * lv[i]) * ep[i] - L.ws[L.w.m0 + d0 + i] : 0.f;      // from the tables' origin
             }
         }
         *reinterpret_cast<float4*>(Xz + d0) = make_float4(z[0] * z[0], z[1] * z[1], z[2] * z[2], z[3] * z[3]);
@@ -547,10 +583,16 @@ int vade_eval_mfma_launch(hipStream_t s, const VadeEvalArgs& a) {
     const int nrb = a.B_pad / 16;
     const double n = a.rows.n_valid;
     {
+        ProfScope ps(s, "vade_origin", 0.0, 16.0 * a.K * a.D);
+        DMVAE_LAUNCH(vade_origin_kernel, dim3((w.Dp + 255) / 256), dim3(256), 0, s, a.prior_means, a.prior_log_vars, a.K, a.D, w.Dp, a.ws + w.m0);
+    }
+    int rc = check_launch("vade_origin");
+    if (rc) return rc;
+    {
         ProfScope ps(s, "vade_tables", 0.0, 24.0 * a.K * a.D);
         DMVAE_LAUNCH(vade_tables_kernel, dim3(w.Kp), dim3(256), 0, s, a.prior_means, a.prior_log_vars, a.K, a.D, w, a.ws);
     }
-    int rc = check_launch("vade_tables");
+    rc = check_launch("vade_tables");
     if (rc) return rc;
     for (int j = 0; j < a.draws; ++j) {
         {
