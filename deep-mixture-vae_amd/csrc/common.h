@@ -78,6 +78,35 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// the same over the 16 lanes that share a row (the row kernels of the latent stage and its kin): every lane gets the result
+__device__ __forceinline__ float row_sum16(float v) {
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
+    return v;
+}
+// three sums step by step.  Not the same code as three calls: side by side the compiler pairs two of the sums into packed adds and keeps the pair
+// packed in the arithmetic that follows (latent_post's dlogits), which decides where it contracts a multiply into an FMA -- the last bit of the result
+__device__ __forceinline__ void row_sum16(float& a, float& b, float& c) {
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 16); b += __shfl_xor(b, o, 16); c += __shfl_xor(c, o, 16);
+    }
+}
+__device__ __forceinline__ float row_max16(float v) {
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 16));
+    return v;
+}
+__device__ __forceinline__ double row_max16(double v) {
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 16));
+    return v;
+}
+__device__ __forceinline__ float row_min16(float v) {
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 16));
+    return v;
+}
 
 // Fixed-order block sum for 256-thread blocks; result valid in thread 0.
 __device__ __forceinline__ float block_sum_256(float v, float* red /* >= 4 floats LDS */) {

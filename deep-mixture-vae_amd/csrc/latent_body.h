@@ -13,17 +13,6 @@ struct LatentLaunch {
     int nchunks;
 };
 
-__device__ __forceinline__ float row_sum16(float v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
-    return v;
-}
-__device__ __forceinline__ float row_max16(float v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 16));
-    return v;
-}
-
 #include "measure.h"      // MEAS_LAT_STAMP: phase stamps of block 0 in the abl7 measurement build (tools/latent_time.py); empty in the product build
 
 // The block's mean / log_var / logits rows when they come from LDS instead of global memory (FUSED: heads_latent.hip, where the workgroup has just

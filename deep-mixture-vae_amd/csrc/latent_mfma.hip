@@ -19,35 +19,22 @@
 // The [B, K, D] tensor TensorFlow materialises is still never formed; the intermediates are [B, 2D] and [B, K].
 // No float atomics: G3's split over the batch writes slabs.  Device noise: one Philox block per four columns of a
 // row, keyed by the element index (a different, equally valid stream than latent.hip's geometry-keyed one).
-#include <algorithm>
-
-#include "latent_tables.h"
+// What a row goes through per quad of columns (load, reparameterisation, the Z / Z_f32 / clv stores), the slab sums and the prior-table
+// gradients are latent_mfma_rows.h's, shared with VaDE's form (latent_vade_mfma.hip); the scratch head and slice rule are latent_tables.h's.
+#include "latent_mfma_rows.h"
 
 namespace dmvae {
 
-struct LatentMfmaWs {      // float offsets into the caller's scratch
-    int Dp, Kp, XW, nsplit, nsplit_s;      // K slices of G3 (over the batch) and of G2 (over 2D)
-    int64_t T1, T2, c2, ck, Wm, X1, AC, S, RL, G, total;
+struct LatentMfmaWs : LatentWsHead {      // float offsets into the caller's scratch
+    int64_t Wm, X1, AC, S, RL, G, total;
 };
 static LatentMfmaWs latent_mfma_layout(int Bp, int D, int K) {
     LatentMfmaWs w;
-    w.Dp = pad64i(D); w.Kp = pad64i(K); w.XW = 2 * w.Dp + 64;
-    const int tiles = (w.Kp / 64) * (w.XW / 64);
-    int ns = 1;
-    while (ns < 32 && tiles * ns < 512 && (Bp / 64) % (2 * ns) == 0) ns *= 2;      // slices of the batch: fill the chip, stay multiples of 64 rows
-    w.nsplit = ns;
-    // G2 = [B, 2D] x [2D, K]: with few clusters (N = K padded to 64) its grid is B / 64 workgroups of a long K loop -- cut 2D
-    int nss = 1;
-    while (nss < 8 && (Bp / 64) * (w.Kp / 64) * nss < 512 && (2 * w.Dp / 64) % (2 * nss) == 0) nss *= 2;
-    w.nsplit_s = nss;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { const int64_t r = o; o += (n + 63) / 64 * 64; return r; };
-    w.T1 = take((int64_t)w.Kp * 2 * w.Dp); w.T2 = take((int64_t)w.Kp * 2 * w.Dp);
-    w.c2 = take(w.Kp); w.ck = take(w.Kp);
+    WsTake take = latent_ws_head(w, Bp, D, K, 1, 8);
     w.Wm = take((int64_t)Bp * w.Kp); w.X1 = take((int64_t)Bp * w.XW);
-    w.AC = take((int64_t)Bp * 2 * w.Dp); w.S = take((int64_t)nss * Bp * w.Kp); w.RL = take(Bp);
-    w.G = take((int64_t)ns * w.Kp * w.XW);
-    w.total = o;
+    w.AC = take((int64_t)Bp * 2 * w.Dp); w.S = take((int64_t)w.nsplit_s * Bp * w.Kp); w.RL = take(Bp);
+    w.G = take((int64_t)w.nsplit * w.Kp * w.XW);
+    w.total = take.o;
     return w;
 }
 
@@ -66,8 +53,7 @@ __global__ __launch_bounds__(256) void latent_pre_kernel(LatentMfmaArgs L, int n
     const dmvae_latent_args& a = L.a;
     if ((int)blockIdx.x >= nrow_blocks) {        // extra workgroups: the prior tables as GEMM operands
         __shared__ float tred[8];
-        latent_tables_block((int)blockIdx.x - nrow_blocks, a.prior_means, a.prior_log_vars, nullptr, a.K, a.D, L.w.Kp, L.w.Dp, L.ws + L.w.T1, L.ws + L.w.T2,
-                            L.ws + L.w.c2, L.ws + L.w.ck, tred);
+        latent_tables_block((int)blockIdx.x - nrow_blocks, a.prior_means, a.prior_log_vars, nullptr, a.K, a.D, L.w, L.ws, tred);
         return;
     }
     const int lane16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
@@ -102,13 +88,11 @@ __global__ __launch_bounds__(256) void latent_pre_kernel(LatentMfmaArgs L, int n
         float mx = -INFINITY;
 #pragma unroll
         for (int j = 0; j < 4; ++j) mx = in[j] ? fmaxf(mx, v[j]) : mx;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 16));
+        mx = row_max16(mx);
         float se = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) se += in[j] ? __expf(v[j] - mx) : 0.f;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) se += __shfl_xor(se, o, 16);
+        se = row_sum16(se);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int k = lane16 + 16 * j;
@@ -131,8 +115,7 @@ __global__ __launch_bounds__(256) void latent_pre_kernel(LatentMfmaArgs L, int n
 #pragma unroll
             for (int j = 0; j < 4; ++j) mx = k0 + 16 * j < K ? fmaxf(mx, valid ? v[j] : 0.f) : mx;
         }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 16));
+        mx = row_max16(mx);
         float se = 0.f;
         for (int k0 = lane16; k0 < K; k0 += 64) {
             float v[4];
@@ -141,8 +124,7 @@ __global__ __launch_bounds__(256) void latent_pre_kernel(LatentMfmaArgs L, int n
 #pragma unroll
             for (int j = 0; j < 4; ++j) se += k0 + 16 * j < K ? __expf((valid ? v[j] : 0.f) - mx) : 0.f;
         }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) se += __shfl_xor(se, o, 16);
+        se = row_sum16(se);
         for (int k0 = lane16; k0 < Kp; k0 += 64) {
             float v[4];
 #pragma unroll
@@ -162,130 +144,50 @@ __global__ __launch_bounds__(256) void latent_pre_kernel(LatentMfmaArgs L, int n
             }
         }
     }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) kc += __shfl_xor(kc, o, 16);
-    kc_acc += kc;
+    kc_acc += row_sum16(kc);
 
-    // columns in quads: Z, reparameterisation coefficient, [e + mu^2 | mu]
-    const bool vec = (D % 4 == 0) && (a.ld_mean % 4 == 0) && (a.ld_log_var % 4 == 0) && (a.ld_g % 4 == 0) && (a.ld_Z % 4 == 0) &&
-                     (!a.eps || a.ld_eps % 4 == 0) && (!a.Z_f32 || a.ld_Zf % 4 == 0);
+    // columns in quads: Z, reparameterisation coefficient, [e + mu^2 | mu] (latent_mfma_rows.h)
+    const bool vec = latent_quads_aligned(a);
+    const float* mrow = a.mean + br * a.ld_mean;
+    const float* vrow = a.log_var + br * a.ld_log_var;
+    const float* erow = a.eps ? a.eps + br * a.ld_eps : nullptr;
     float lvsum = 0.f;
+    auto quad = [&](int q4, float (&mu)[4], const float (&lv)[4], float (&ep)[4], const bool (&ok)[4]) {      // one quad from its loaded values
+        const int d0 = 4 * q4;
+        if (ok[0] && !a.eps) philox_normal4(a.seed, nstep, 0u, (uint64_t)b * (Dp / 4) + q4, ep);
+        float z[4], cl[4], x1[4], zs[4];
+        reparam_quad(mu, lv, ep, ok, nullptr, z, cl, x1, zs, lvsum);
+        *reinterpret_cast<float4*>(X1 + d0) = make_float4(x1[0], x1[1], x1[2], x1[3]);
+        *reinterpret_cast<float4*>(X1 + Dp + d0) = make_float4(mu[0], mu[1], mu[2], mu[3]);
+        store_z_quad(a, b, d0, vec, z, cl);
+    };
     if (vec) {
-        // four quads per lane and trip: their 12 loads issued together, unconditionally (pad rows read row 0, pad quads read quad 0); the outputs
-        // as 8- / 16-byte stores.  Same arithmetic as the general loop below.
-        const float* mrow = a.mean + br * a.ld_mean;
-        const float* vrow = a.log_var + br * a.ld_log_var;
-        const float* erow = a.eps ? a.eps + br * a.ld_eps : nullptr;
+        // four quads per lane and trip: their 12 loads issued together; the outputs as 8- / 16-byte stores.  Same arithmetic as the general loop below.
         const int nq = Dp / 4;
         for (int q0 = lane16; q0 < nq; q0 += 64) {
-            float4 m4[4], l4[4], e4[4];
+            float mu[4][4], lv[4][4], ep[4][4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) load_quad(mrow, vrow, erow, true, 4 * (q0 + 16 * u), D, mu[u], lv[u], ep[u]);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const int d0 = 4 * (q0 + 16 * u);
-                const int off = (q0 + 16 * u < nq && d0 < D) ? d0 : 0;
-                m4[u] = *reinterpret_cast<const float4*>(mrow + off);
-                l4[u] = *reinterpret_cast<const float4*>(vrow + off);
-                e4[u] = erow ? *reinterpret_cast<const float4*>(erow + off) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int q4 = q0 + 16 * u, d0 = 4 * q4;
+                const int q4 = q0 + 16 * u;
                 if (q4 >= nq) continue;
-                const bool in = valid && d0 < D;            // (D % 4 == 0 here: the whole quad)
-                float mu[4] = {in ? m4[u].x : 0.f, in ? m4[u].y : 0.f, in ? m4[u].z : 0.f, in ? m4[u].w : 0.f};
-                const float lv[4] = {in ? l4[u].x : 0.f, in ? l4[u].y : 0.f, in ? l4[u].z : 0.f, in ? l4[u].w : 0.f};
-                float ep[4] = {in ? e4[u].x : 0.f, in ? e4[u].y : 0.f, in ? e4[u].z : 0.f, in ? e4[u].w : 0.f};
-                if (in && !a.eps) philox_normal4(a.seed, nstep, 0u, (uint64_t)b * (Dp / 4) + q4, ep);
-                float z[4], cl[4], x1[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float e = __expf(lv[j]), sd = __expf(0.5f * lv[j]);
-                    z[j] = in ? mu[j] + sd * ep[j] : 0.f;
-                    cl[j] = in ? ep[j] * 0.5f * sd : 0.f;
-                    x1[j] = in ? e + mu[j] * mu[j] : 0.f;
-                    lvsum += in ? lv[j] : 0.f;
-                }
-                *reinterpret_cast<float4*>(X1 + d0) = make_float4(x1[0], x1[1], x1[2], x1[3]);
-                *reinterpret_cast<float4*>(X1 + Dp + d0) = make_float4(mu[0], mu[1], mu[2], mu[3]);
-                if (d0 + 4 <= a.ld_Z) {
-                    if (a.act_dtype == DMVAE_BF16) {
-                        uint2 pk;
-                        pk.x = pack2bf(z[0], z[1]); pk.y = pack2bf(z[2], z[3]);
-                        *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(a.Z_act) + (int64_t)b * a.ld_Z + d0) = pk;
-                    } else *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.Z_act) + (int64_t)b * a.ld_Z + d0) = make_float4(z[0], z[1], z[2], z[3]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (d0 + j < a.ld_Z) {
-                            if (a.act_dtype == DMVAE_BF16) reinterpret_cast<bf16_t*>(a.Z_act)[(int64_t)b * a.ld_Z + d0 + j] = f2bf(z[j]);
-                            else reinterpret_cast<float*>(a.Z_act)[(int64_t)b * a.ld_Z + d0 + j] = z[j];
-                        }
-                }
-                if (d0 < D) {
-                    if (a.Z_f32) *reinterpret_cast<float4*>(a.Z_f32 + (int64_t)b * a.ld_Zf + d0) = make_float4(z[0], z[1], z[2], z[3]);
-                    *reinterpret_cast<float4*>(a.clv + (int64_t)b * a.ld_g + d0) = make_float4(cl[0], cl[1], cl[2], cl[3]);
-                }
+                const bool in = valid && 4 * q4 < D;            // (D % 4 == 0 here: the whole quad)
+                const bool ok[4] = {in, in, in, in};
+                quad(q4, mu[u], lv[u], ep[u], ok);
             }
         }
     } else
     for (int q4 = lane16; q4 < Dp / 4; q4 += 16) {
         const int d0 = 4 * q4;
-        float mu[4] = {0.f, 0.f, 0.f, 0.f}, lv[4] = {0.f, 0.f, 0.f, 0.f}, ep[4] = {0.f, 0.f, 0.f, 0.f};
-        if (valid && d0 < D) {
-            if (vec) {
-                const float4 m4 = *reinterpret_cast<const float4*>(a.mean + (int64_t)b * a.ld_mean + d0);
-                const float4 l4 = *reinterpret_cast<const float4*>(a.log_var + (int64_t)b * a.ld_log_var + d0);
-                mu[0] = m4.x; mu[1] = m4.y; mu[2] = m4.z; mu[3] = m4.w;
-                lv[0] = l4.x; lv[1] = l4.y; lv[2] = l4.z; lv[3] = l4.w;
-                if (a.eps) {
-                    const float4 e4 = *reinterpret_cast<const float4*>(a.eps + (int64_t)b * a.ld_eps + d0);
-                    ep[0] = e4.x; ep[1] = e4.y; ep[2] = e4.z; ep[3] = e4.w;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (d0 + j < D) {
-                        mu[j] = a.mean[(int64_t)b * a.ld_mean + d0 + j];
-                        lv[j] = a.log_var[(int64_t)b * a.ld_log_var + d0 + j];
-                        if (a.eps) ep[j] = a.eps[(int64_t)b * a.ld_eps + d0 + j];
-                    }
-            }
-            if (!a.eps) philox_normal4(a.seed, nstep, 0u, (uint64_t)b * (Dp / 4) + q4, ep);
-        }
-        float z[4], cl[4], x1[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool ok = valid && d0 + j < D;
-            const float e = __expf(lv[j]), sd = __expf(0.5f * lv[j]);
-            z[j] = ok ? mu[j] + sd * ep[j] : 0.f;
-            cl[j] = ok ? ep[j] * 0.5f * sd : 0.f;
-            x1[j] = ok ? e + mu[j] * mu[j] : 0.f;
-            if (!ok) mu[j] = 0.f;
-            lvsum += ok ? lv[j] : 0.f;
-        }
-        *reinterpret_cast<float4*>(X1 + d0) = make_float4(x1[0], x1[1], x1[2], x1[3]);
-        *reinterpret_cast<float4*>(X1 + Dp + d0) = make_float4(mu[0], mu[1], mu[2], mu[3]);
-        // outputs: Z (act dtype, pad columns up to ld_Z zeroed: they are K padding of the first decoder GEMM), f32 copy, coefficient
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int d = d0 + j;
-            if (d < a.ld_Z) {
-                if (a.act_dtype == DMVAE_BF16) reinterpret_cast<bf16_t*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = f2bf(z[j]);
-                else reinterpret_cast<float*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = z[j];
-            }
-            if (d < D) {
-                if (a.Z_f32) a.Z_f32[(int64_t)b * a.ld_Zf + d] = z[j];
-                a.clv[(int64_t)b * a.ld_g + d] = cl[j];
-            }
-        }
+        float mu[4], lv[4], ep[4];
+        load_quad(mrow, vrow, erow, false, d0, D, mu, lv, ep);
+        const bool ok[4] = {valid && d0 < D, valid && d0 + 1 < D, valid && d0 + 2 < D, valid && d0 + 3 < D};
+        quad(q4, mu, lv, ep, ok);
     }
-    for (int d = Dp + lane16; d < a.ld_Z; d += 16) {      // (a Z buffer wider than D padded to 64)
-        if (a.act_dtype == DMVAE_BF16) reinterpret_cast<bf16_t*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = 0;
-        else reinterpret_cast<float*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = 0.f;
-    }
-    for (int c = lane16; c < 64; c += 16) X1[2 * Dp + c] = (c == 0 && valid) ? 1.f : 0.f;      // the ones column: G3 then also yields sum_b w_bk
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) lvsum += __shfl_xor(lvsum, o, 16);
+    zero_z_tail(a, b, Dp, lane16);
+    write_ones_column(X1 + 2 * Dp, lane16, valid);      // G3 then also yields sum_b w_bk
+    lvsum = row_sum16(lvsum);
     if (lane16 == 0) L.ws[L.w.RL + b] = lvsum;
   }
     if (lane16 == 0) red[rsub] = kc_acc;
@@ -306,19 +208,7 @@ __global__ __launch_bounds__(256) void latent_post_kernel(LatentMfmaArgs L, int 
     const float klr = st ? st->kl_ratio : a.kl_ratio;
     const float rB = klr * a.inv_B, rB2 = 0.5f * rB;
     if ((int)blockIdx.x >= nrow_blocks) {
-        const int64_t KD = (int64_t)K * D;
-        for (int64_t idx = (int64_t)((int)blockIdx.x - nrow_blocks) * 256 + threadIdx.x; idx < KD; idx += (int64_t)((int)gridDim.x - nrow_blocks) * 256) {
-            const int k = (int)(idx / D), d = (int)(idx - (int64_t)k * D);
-            float ge = 0.f, gm = 0.f, wsum = 0.f;
-            for (int s = 0; s < L.w.nsplit; ++s) {                     // slabs in ascending order
-                const float* g = L.ws + L.w.G + ((int64_t)s * Kp + k) * XW;
-                ge += g[d]; gm += g[Dp + d]; wsum += g[2 * Dp];
-            }
-            const float ip = L.ws[L.w.T1 + (int64_t)k * 2 * Dp + d];
-            const float pmv = a.prior_means[idx];
-            a.dprior_partials[idx] = -rB * ip * (gm - pmv * wsum);
-            a.dprior_partials[KD + idx] = rB2 * (wsum - ip * (ge - 2.f * pmv * gm + pmv * pmv * wsum));
-        }
+        prior_grad_from_slabs<false>(L.w, L.ws, L.w.G, a.prior_means, nullptr, K, D, rB, a.dprior_partials, nrow_blocks);
         return;
     }
     const int lane16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
@@ -330,7 +220,7 @@ __global__ __launch_bounds__(256) void latent_post_kernel(LatentMfmaArgs L, int 
     const float* AC = L.ws + L.w.AC + (int64_t)b * 2 * Dp;
     const float* S0 = L.ws + L.w.S + (int64_t)b * Kp;
     const int64_t sstr = (int64_t)a.B_pad * Kp;       // slab stride of G2's K slices
-    auto Ssum = [&](int k) { float v = S0[k]; for (int sl = 1; sl < L.w.nsplit_s; ++sl) v += S0[sl * sstr + k]; return v; };
+    auto Ssum = [&](int k) { float v; slab_sum<float, 1>(S0, sstr, L.w.nsplit_s, &k, &v); return v; };
     const float* Wm = L.ws + L.w.Wm + (int64_t)b * Kp;
     const float* X1 = L.ws + L.w.X1 + (int64_t)b * XW;
     // gradients wrt mean / log_var.  Aligned shapes: four quads per lane and trip, every load unconditional (a pad row reads row 0 of log_var),
@@ -390,20 +280,15 @@ __global__ __launch_bounds__(256) void latent_post_kernel(LatentMfmaArgs L, int 
         float w[4], t[4], dq[4];
         bool in[4];
         float ss[4], c2v[4], ckv[4];
+        int kk[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int k = lane16 + 16 * j;
             in[j] = k < K;
-            const int kk = in[j] ? k : 0;
-            w[j] = Wm[kk]; ss[j] = S0[kk]; c2v[j] = L.ws[L.w.c2 + kk]; ckv[j] = L.ws[L.w.ck + kk];
+            kk[j] = in[j] ? k : 0;
+            w[j] = Wm[kk[j]]; c2v[j] = L.ws[L.w.c2 + kk[j]]; ckv[j] = L.ws[L.w.ck + kk[j]];
         }
-        for (int sl = 1; sl < L.w.nsplit_s; ++sl) {
-            float sv[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) sv[j] = S0[sl * sstr + (in[j] ? lane16 + 16 * j : 0)];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ss[j] += sv[j];
-        }
+        slab_sum<float, 4>(S0, sstr, L.w.nsplit_s, kk, ss);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             t[j] = ss[j] + c2v[j] + ckv[j] - rl - (float)D;
@@ -414,10 +299,7 @@ __global__ __launch_bounds__(256) void latent_post_kernel(LatentMfmaArgs L, int 
                 s_qdq += w[j] * dq[j];
             }
         }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) {
-            s_wdw += __shfl_xor(s_wdw, o, 16); s_qdq += __shfl_xor(s_qdq, o, 16); klz += __shfl_xor(klz, o, 16);
-        }
+        row_sum16(s_wdw, s_qdq, klz);
         for (int k = lane16; k < a.ld_dl; k += 16) {
             float dl = 0.f;
             const int j = (k - lane16) >> 4;
@@ -441,10 +323,7 @@ __global__ __launch_bounds__(256) void latent_post_kernel(LatentMfmaArgs L, int 
         s_wdw += w * (rB2 * t);
         s_qdq += w * dq;
     }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-        s_wdw += __shfl_xor(s_wdw, o, 16); s_qdq += __shfl_xor(s_qdq, o, 16); klz += __shfl_xor(klz, o, 16);
-    }
+    row_sum16(s_wdw, s_qdq, klz);
     for (int k = lane16; k < a.ld_dl; k += 16) {
         float dl = 0.f;
         if (k < K && valid) {
@@ -476,11 +355,9 @@ int latent_mfma_launch(hipStream_t s, const dmvae_latent_args* a, float* ws, int
     L.RB = a->B_pad / latent_nblocks(a->B_pad, a->D, a->K);        // latent.hip's rows per workgroup (16, 32 or 64)
     const int nrb = a->B_pad / L.RB;
     const double BD = (double)a->B * a->D, BK = (double)a->B * a->K;
-    {   // the prior-table operands ride as Kp extra workgroups of the row kernel (one launch less)
-        ProfScope ps(s, "latent_pre", 0.0, 4.0 * (BD * (2.0 + (a->eps ? 1.0 : 0.0) + 2.0 + 2.0 + 1.0) + BK * 3.0) + 16.0 * a->K * a->D);
-        DMVAE_LAUNCH(latent_pre_kernel, dim3(nrb + w.Kp), dim3(256), 0, s, L, nrb);
-    }
-    int rc = check_launch("latent_pre");
+    // the prior-table operands ride as Kp extra workgroups of the row kernel (one launch less)
+    int rc = latent_launch_rows(s, "latent_pre", 4.0 * (BD * (2.0 + (a->eps ? 1.0 : 0.0) + 2.0 + 2.0 + 1.0) + BK * 3.0) + 16.0 * a->K * a->D, latent_pre_kernel,
+                                nrb + w.Kp, L, nrb);
     if (rc) return rc;
     {
         ProfScope ps(s, "latent_gemm_f32", 2.0 * a->B_pad * (double)w.Kp * (2.0 * w.Dp + 2.0 * w.Dp + w.XW), 4.0 * a->B_pad * (3.0 * w.Kp + 2.0 * w.XW + 2.0 * w.Dp));
@@ -492,12 +369,8 @@ int latent_mfma_launch(hipStream_t s, const dmvae_latent_args* a, float* ws, int
         rc = gemm_f32_trio(s, g1, 1, g2, w.nsplit_s, g3, w.nsplit);
     }
     if (rc) return rc;
-    {
-        const int extra = (int)std::min<int64_t>(256, ((int64_t)a->K * a->D + 255) / 256);
-        ProfScope ps(s, "latent_post", 0.0, 4.0 * (BD * (2.0 + 1.0 + 1.0 + 2.0) + BK * 3.0) + 4.0 * w.nsplit * w.Kp * w.XW);
-        DMVAE_LAUNCH(latent_post_kernel, dim3(nrb + extra), dim3(256), 0, s, L, nrb);
-    }
-    return check_launch("latent_post");
+    return latent_launch_rows(s, "latent_post", 4.0 * (BD * (2.0 + 1.0 + 1.0 + 2.0) + BK * 3.0) + 4.0 * w.nsplit * w.Kp * w.XW, latent_post_kernel,
+                              nrb + prior_grad_workgroups(a->K, a->D), L, nrb);
 }
 
 }  // namespace dmvae

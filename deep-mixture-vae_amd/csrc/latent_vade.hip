@@ -21,17 +21,6 @@
 
 namespace dmvae {
 
-__device__ __forceinline__ float sum16(float v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
-    return v;
-}
-__device__ __forceinline__ float max16(float v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 16));
-    return v;
-}
-
 __global__ __launch_bounds__(256) void latent_vade_kernel(dmvae_latent_args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int K = a.K, D = a.D, DP = D + 1;
@@ -73,7 +62,7 @@ __global__ __launch_bounds__(256) void latent_vade_kernel(dmvae_latent_args a) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) s += t[i];
         }
-        s = sum16(s);
+        s = row_sum16(s);
         if (lr == 0) ck[k] = s;
     }
     // reparameterisation: lane owns d = lr + 16 i
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(256) void latent_vade_kernel(dmvae_latent_args a) {
         if (a.act_dtype == DMVAE_BF16) reinterpret_cast<bf16_t*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = f2bf(z);     // pad columns: zeros
         else reinterpret_cast<float*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = z;
     }
-    lvsum = sum16(lvsum);
+    lvsum = row_sum16(lvsum);
     __syncthreads();
 
     // responsibilities: lane owns k = lr + 16 j
@@ -117,14 +106,14 @@ __global__ __launch_bounds__(256) void latent_vade_kernel(dmvae_latent_args a) {
         dus[rsub * K + k] = ck[k] - lvsum - (float)D + stt;        // T_k for now
         mx = fmaxf(mx, u);
     }
-    mx = max16(mx);
+    mx = row_max16(mx);
     float se = 0.f;
     for (int k = lr; k < K; k += 16) {
         const float ex = __expf(gam[rsub * K + k] - mx);
         gam[rsub * K + k] = ex;
         se += ex;
     }
-    se = sum16(se);
+    se = row_sum16(se);
     float sgG = 0.f, klz = 0.f, klc = 0.f;
     for (int k = lr; k < K; k += 16) {
         const float g = valid ? gam[rsub * K + k] / se : 0.f;
@@ -138,7 +127,7 @@ __global__ __launch_bounds__(256) void latent_vade_kernel(dmvae_latent_args a) {
         klc += g * (lg + logK);
         if (a.weights) a.weights[(int64_t)b * a.ld_w + k] = g;
     }
-    sgG = sum16(sgG); klz = sum16(klz); klc = sum16(klc);
+    sgG = row_sum16(sgG); klz = row_sum16(klz); klc = row_sum16(klc);
     for (int k = lr; k < K; k += 16) dus[rsub * K + k] = gam[rsub * K + k] * (dus[rsub * K + k] - sgG);      // du
     __syncthreads();
 

@@ -31,39 +31,25 @@
 //
 // The evaluation (eval_clusters.hip: averaged responsibilities of `draws` samples) at these shapes is the forward half per
 // draw: vade_eval_z, G2 on the sample rows alone, vade_eval_rows; its noise is keyed exactly as vade_eval_kernel keys it.
-#include <algorithm>
-
+// The quad code of vade_pre and vade_eval_z, the slab sums and the prior-table gradients are latent_mfma_rows.h's, shared with DMVAE's form;
+// the scratch head and its slice rule are latent_tables.h's.  What stays different from latent_mfma.hip on purpose: one quad per lane and trip,
+// the scores added in double with an extra pass over the slabs, the origin.
 #include "eval_clusters.h"
-#include "latent_body.h"
-#include "latent_tables.h"
+#include "latent_mfma_rows.h"
 
 namespace dmvae {
 
-struct VadeMfmaWs {        // float offsets into the caller's scratch
-    int Dp, Kp, XW, nsplit, nsplit_s;      // K slices of each half of G3 (over the batch) and of G2 (over 2D)
-    int64_t T1, T2, c2, ck, X, S, RL, W2, AC, G, m0, total;
+struct VadeMfmaWs : LatentWsHead {        // float offsets into the caller's scratch; nsplit counts the slices of EACH half of G3
+    int64_t X, S, RL, W2, AC, G, m0, total;
 };
 static VadeMfmaWs vade_mfma_layout(int Bp, int D, int K) {
     VadeMfmaWs w;
-    w.Dp = pad64i(D); w.Kp = pad64i(K); w.XW = 2 * w.Dp + 64;
-    const int tiles = (w.Kp / 64) * (w.XW / 64);
-    int ns = 1;
-    while (ns < 32 && tiles * 2 * ns < 512 && (Bp / 64) % (2 * ns) == 0) ns *= 2;      // slices of the batch (per half): fill the chip, stay multiples of 64 rows
-    w.nsplit = ns;
-    // G2 = [2B, 2D] x [2D, K]: with few rows and clusters its grid is a handful of workgroups of a long K loop -- cut 2D.  (Shorter fmaf
-    // chains are also what keeps u accurate at D = 512; a full chip takes the one-slice form.)
-    int nss = 1;
-    while (nss < 16 && (2 * Bp / 64) * (w.Kp / 64) * nss < 512 && (2 * w.Dp / 64) % (2 * nss) == 0) nss *= 2;
-    w.nsplit_s = nss;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { const int64_t r = o; o += (n + 63) / 64 * 64; return r; };
-    w.T1 = take((int64_t)w.Kp * 2 * w.Dp); w.T2 = take((int64_t)w.Kp * 2 * w.Dp);
-    w.c2 = take(w.Kp); w.ck = take(w.Kp);
-    w.X = take((int64_t)2 * Bp * w.XW); w.S = take((int64_t)nss * 2 * Bp * w.Kp); w.RL = take(Bp);
+    WsTake take = latent_ws_head(w, Bp, D, K, 2, 16);
+    w.X = take((int64_t)2 * Bp * w.XW); w.S = take((int64_t)w.nsplit_s * 2 * Bp * w.Kp); w.RL = take(Bp);
     w.W2 = take((int64_t)2 * Bp * w.Kp); w.AC = take((int64_t)2 * Bp * 2 * w.Dp);
-    w.G = take((int64_t)2 * ns * w.Kp * w.XW);
+    w.G = take((int64_t)2 * w.nsplit * w.Kp * w.XW);
     w.m0 = take(w.Dp);
-    w.total = o;
+    w.total = take.o;
     return w;
 }
 
@@ -106,10 +92,13 @@ __global__ __launch_bounds__(256) void vade_origin_kernel(const float* __restric
     }
     m0[d] = v;
 }
+static int vade_origin_launch(hipStream_t s, const float* pm, const float* plv, int K, int D, const VadeMfmaWs& w, float* ws) {
+    return latent_launch_rows(s, "vade_origin", 16.0 * K * D, vade_origin_kernel, (w.Dp + 255) / 256, pm, plv, K, D, w.Dp, ws + w.m0);
+}
 
 __global__ __launch_bounds__(256) void vade_tables_kernel(const float* pm, const float* plv, int K, int D, VadeMfmaWs w, float* ws) {
     __shared__ float tred[8];
-    latent_tables_block((int)blockIdx.x, pm, plv, ws + w.m0, K, D, w.Kp, w.Dp, ws + w.T1, ws + w.T2, ws + w.c2, ws + w.ck, tred);
+    latent_tables_block((int)blockIdx.x, pm, plv, ws + w.m0, K, D, w, ws, tred);
 }
 
 // ---- rows, before the GEMMs.  16 lanes per row, 16 rows per 256-thread block; a lane owns quads of columns.
@@ -117,8 +106,7 @@ __global__ __launch_bounds__(256) void vade_pre_kernel(VadeMfmaArgs L, int nrow_
     const dmvae_latent_args& a = L.a;
     if ((int)blockIdx.x >= nrow_blocks) {        // extra workgroups: the prior tables as GEMM operands
         __shared__ float tred[8];
-        latent_tables_block((int)blockIdx.x - nrow_blocks, a.prior_means, a.prior_log_vars, L.ws + L.w.m0, a.K, a.D, L.w.Kp, L.w.Dp, L.ws + L.w.T1, L.ws + L.w.T2,
-                            L.ws + L.w.c2, L.ws + L.w.ck, tred);
+        latent_tables_block((int)blockIdx.x - nrow_blocks, a.prior_means, a.prior_log_vars, L.ws + L.w.m0, a.K, a.D, L.w, L.ws, tred);
         return;
     }
     const int lane16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
@@ -133,81 +121,27 @@ __global__ __launch_bounds__(256) void vade_pre_kernel(VadeMfmaArgs L, int nrow_
     const float* mrow = a.mean + br * a.ld_mean;
     const float* vrow = a.log_var + br * a.ld_log_var;
     const float* erow = a.eps ? a.eps + br * a.ld_eps : nullptr;
-    const bool vec = (D % 4 == 0) && (a.ld_mean % 4 == 0) && (a.ld_log_var % 4 == 0) && (a.ld_g % 4 == 0) && (a.ld_Z % 4 == 0) &&
-                     (!a.eps || a.ld_eps % 4 == 0) && (!a.Z_f32 || a.ld_Zf % 4 == 0);
+    const bool vec = latent_quads_aligned(a);
     float lvsum = 0.f;
     for (int q4 = lane16; q4 < Dp / 4; q4 += 16) {
         const int d0 = 4 * q4;
-        float mu[4] = {0.f, 0.f, 0.f, 0.f}, lv[4] = {0.f, 0.f, 0.f, 0.f}, ep[4] = {0.f, 0.f, 0.f, 0.f};
-        if (vec) {                               // (D % 4 == 0: a quad is inside the row or outside it)
-            const int off = d0 < D ? d0 : 0;
-            const float4 m4 = *reinterpret_cast<const float4*>(mrow + off);
-            const float4 l4 = *reinterpret_cast<const float4*>(vrow + off);
-            const float4 e4 = erow ? *reinterpret_cast<const float4*>(erow + off) : make_float4(0.f, 0.f, 0.f, 0.f);
-            mu[0] = m4.x; mu[1] = m4.y; mu[2] = m4.z; mu[3] = m4.w;
-            lv[0] = l4.x; lv[1] = l4.y; lv[2] = l4.z; lv[3] = l4.w;
-            ep[0] = e4.x; ep[1] = e4.y; ep[2] = e4.z; ep[3] = e4.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int off = d0 + j < D ? d0 + j : 0;
-                mu[j] = mrow[off]; lv[j] = vrow[off];
-                if (erow) ep[j] = erow[off];
-            }
-        }
-        if (valid && d0 < D && !a.eps) philox_normal4(a.seed, nstep, 0u, (uint64_t)b * (Dp / 4) + q4, ep);
+        float mu[4], lv[4], ep[4];
+        load_quad(mrow, vrow, erow, vec, d0, D, mu, lv, ep);
+        const bool ok[4] = {valid && d0 < D, valid && d0 + 1 < D, valid && d0 + 2 < D, valid && d0 + 3 < D};
+        if (ok[0] && !a.eps) philox_normal4(a.seed, nstep, 0u, (uint64_t)b * (Dp / 4) + q4, ep);
         const float4 o4 = *reinterpret_cast<const float4*>(L.ws + L.w.m0 + d0);      // the origin of the GEMM operands (vade_origin_kernel); Z itself is not shifted
         const float org[4] = {o4.x, o4.y, o4.z, o4.w};
         float z[4], cl[4], x1[4], zs[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool ok = valid && d0 + j < D;
-            const float e = __expf(lv[j]), sd = __expf(0.5f * lv[j]);
-            z[j] = ok ? mu[j] + sd * ep[j] : 0.f;
-            cl[j] = ok ? ep[j] * 0.5f * sd : 0.f;
-            mu[j] = ok ? mu[j] - org[j] : 0.f;
-            zs[j] = ok ? z[j] - org[j] : 0.f;
-            x1[j] = ok ? e + mu[j] * mu[j] : 0.f;
-            lvsum += ok ? lv[j] : 0.f;
-        }
+        reparam_quad(mu, lv, ep, ok, org, z, cl, x1, zs, lvsum);
         *reinterpret_cast<float4*>(Xm + d0) = make_float4(x1[0], x1[1], x1[2], x1[3]);
         *reinterpret_cast<float4*>(Xm + Dp + d0) = make_float4(mu[0], mu[1], mu[2], mu[3]);
         *reinterpret_cast<float4*>(Xz + d0) = make_float4(zs[0] * zs[0], zs[1] * zs[1], zs[2] * zs[2], zs[3] * zs[3]);
         *reinterpret_cast<float4*>(Xz + Dp + d0) = make_float4(zs[0], zs[1], zs[2], zs[3]);
-        // outputs: Z (act dtype, pad columns up to ld_Z zeroed: they are K padding of the first decoder GEMM), f32 copy, coefficient
-        if (vec && d0 + 4 <= a.ld_Z) {
-            if (a.act_dtype == DMVAE_BF16) {
-                uint2 pk;
-                pk.x = pack2bf(z[0], z[1]); pk.y = pack2bf(z[2], z[3]);
-                *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(a.Z_act) + (int64_t)b * a.ld_Z + d0) = pk;
-            } else *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.Z_act) + (int64_t)b * a.ld_Z + d0) = make_float4(z[0], z[1], z[2], z[3]);
-            if (d0 < D) {
-                if (a.Z_f32) *reinterpret_cast<float4*>(a.Z_f32 + (int64_t)b * a.ld_Zf + d0) = make_float4(z[0], z[1], z[2], z[3]);
-                *reinterpret_cast<float4*>(a.clv + (int64_t)b * a.ld_g + d0) = make_float4(cl[0], cl[1], cl[2], cl[3]);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int d = d0 + j;
-                if (d < a.ld_Z) {
-                    if (a.act_dtype == DMVAE_BF16) reinterpret_cast<bf16_t*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = f2bf(z[j]);
-                    else reinterpret_cast<float*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = z[j];
-                }
-                if (d < D) {
-                    if (a.Z_f32) a.Z_f32[(int64_t)b * a.ld_Zf + d] = z[j];
-                    a.clv[(int64_t)b * a.ld_g + d] = cl[j];
-                }
-            }
-        }
+        store_z_quad(a, b, d0, vec, z, cl);
     }
-    for (int d = Dp + lane16; d < a.ld_Z; d += 16) {      // (a Z buffer wider than D padded to 64)
-        if (a.act_dtype == DMVAE_BF16) reinterpret_cast<bf16_t*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = 0;
-        else reinterpret_cast<float*>(a.Z_act)[(int64_t)b * a.ld_Z + d] = 0.f;
-    }
-    for (int c = lane16; c < 64; c += 16) {                // the ones column: G3 then also yields sum_b gamma and sum_b du
-        Xm[2 * Dp + c] = (c == 0 && valid) ? 1.f : 0.f;
-        Xz[2 * Dp + c] = (c == 0 && valid) ? 1.f : 0.f;
-    }
+    zero_z_tail(a, b, Dp, lane16);
+    write_ones_column(Xm + 2 * Dp, lane16, valid);      // G3 then also yields sum_b gamma and sum_b du
+    write_ones_column(Xz + 2 * Dp, lane16, valid);
     lvsum = row_sum16(lvsum);
     if (lane16 == 0) L.ws[L.w.RL + b] = lvsum;
 }
@@ -215,12 +149,7 @@ __global__ __launch_bounds__(256) void vade_pre_kernel(VadeMfmaArgs L, int nrow_
 // S_k + c2_k + ck_k of four clusters k0 .. k0 + 3 of one row from the K-slice slabs, in double (slabs in ascending order).  k0 < Kp: the pad
 // columns of S, c2 and ck exist (zeros)
 __device__ __forceinline__ void vade_score4(const float* S0, int64_t sstr, int nss, const float* c2, const float* ck, int k0, double v[4]) {
-    const float4 s0 = *reinterpret_cast<const float4*>(S0 + k0);
-    v[0] = (double)s0.x; v[1] = (double)s0.y; v[2] = (double)s0.z; v[3] = (double)s0.w;
-    for (int sl = 1; sl < nss; ++sl) {
-        const float4 t = *reinterpret_cast<const float4*>(S0 + sl * sstr + k0);
-        v[0] += (double)t.x; v[1] += (double)t.y; v[2] += (double)t.z; v[3] += (double)t.w;
-    }
+    slab_sum<double, 4, true>(S0, sstr, nss, &k0, v);
     const float4 p = *reinterpret_cast<const float4*>(c2 + k0), q = *reinterpret_cast<const float4*>(ck + k0);
     v[0] = v[0] + (double)p.x + (double)q.x; v[1] = v[1] + (double)p.y + (double)q.y;
     v[2] = v[2] + (double)p.z + (double)q.z; v[3] = v[3] + (double)p.w + (double)q.w;
@@ -273,8 +202,7 @@ __global__ __launch_bounds__(256) void vade_rows_kernel(VadeMfmaArgs L) {
         }
         *reinterpret_cast<float4*>(dus + k0) = make_float4(T[0], T[1], T[2], T[3]);      // T_k for now
     }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) { mxd = fmax(mxd, __shfl_xor(mxd, o, 16)); tmin = fminf(tmin, __shfl_xor(tmin, o, 16)); }
+    mxd = row_max16(mxd); tmin = row_min16(tmin);
     float se = 0.f;
     for (int k0 = 4 * lane16; k0 < K; k0 += 64) {
         double uz[4];
@@ -335,30 +263,12 @@ __global__ __launch_bounds__(256) void vade_rows_kernel(VadeMfmaArgs L) {
 // ---- rows, after the GEMMs; workgroups >= nrow_blocks: the prior-table gradients from the G slabs
 __global__ __launch_bounds__(256) void vade_post_kernel(VadeMfmaArgs L, int nrow_blocks) {
     const dmvae_latent_args& a = L.a;
-    const int D = a.D, K = a.K, Dp = L.w.Dp, Kp = L.w.Kp, XW = L.w.XW;
+    const int D = a.D, K = a.K, Dp = L.w.Dp, XW = L.w.XW;
     const dmvae_state* st = reinterpret_cast<const dmvae_state*>(a.state);
     const float klr = st ? st->kl_ratio : a.kl_ratio;
     const float rB = klr * a.inv_B, rB2 = 0.5f * rB;
-    if ((int)blockIdx.x >= nrow_blocks) {
-        const int64_t KD = (int64_t)K * D;
-        const int ns = L.w.nsplit;
-        for (int64_t idx = (int64_t)((int)blockIdx.x - nrow_blocks) * 256 + threadIdx.x; idx < KD; idx += (int64_t)((int)gridDim.x - nrow_blocks) * 256) {
-            const int k = (int)(idx / D), d = (int)(idx - (int64_t)k * D);
-            float ge = 0.f, gm = 0.f, wsum = 0.f, gzz = 0.f, gz = 0.f, usum = 0.f;
-            for (int s = 0; s < ns; ++s) {                                   // slabs in ascending order: mean rows, then sample rows
-                const float* g = L.ws + L.w.G + ((int64_t)s * Kp + k) * XW;
-                ge += g[d]; gm += g[Dp + d]; wsum += g[2 * Dp];
-            }
-            for (int s = ns; s < 2 * ns; ++s) {
-                const float* g = L.ws + L.w.G + ((int64_t)s * Kp + k) * XW;
-                gzz += g[d]; gz += g[Dp + d]; usum += g[2 * Dp];
-            }
-            const float ip = L.ws[L.w.T1 + (int64_t)k * 2 * Dp + d];
-            const float pmv = a.prior_means[idx] - L.ws[L.w.m0 + d];      // (the tables' origin: G holds sums of the shifted mean and z)
-            a.dprior_partials[idx] = -rB * ip * (gm - pmv * wsum) + ip * (gz - pmv * usum);
-            a.dprior_partials[KD + idx] = rB2 * (wsum - ip * (ge - 2.f * pmv * gm + pmv * pmv * wsum)) +
-                                          0.5f * (ip * (gzz - 2.f * pmv * gz + pmv * pmv * usum) - usum);
-        }
+    if ((int)blockIdx.x >= nrow_blocks) {      // (the tables' origin: G holds sums of the shifted mean and z)
+        prior_grad_from_slabs<true>(L.w, L.ws, L.w.G, a.prior_means, L.ws + L.w.m0, K, D, rB, a.dprior_partials, nrow_blocks);
         return;
     }
     const int lane16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
@@ -429,28 +339,17 @@ int latent_vade_mfma_launch(hipStream_t s, const dmvae_latent_args* a, float* ws
     L.a = *a; L.w = w; L.ws = ws;
     const int nrb = a->B_pad / 16, Bp2 = 2 * a->B_pad;
     const double BD = (double)a->B * a->D, BK = (double)a->B * a->K;
-    {
-        ProfScope ps(s, "vade_origin", 0.0, 16.0 * a->K * a->D);
-        DMVAE_LAUNCH(vade_origin_kernel, dim3((w.Dp + 255) / 256), dim3(256), 0, s, a->prior_means, a->prior_log_vars, a->K, a->D, w.Dp, ws + w.m0);
-    }
-    int rc = check_launch("vade_origin");
+    int rc = vade_origin_launch(s, a->prior_means, a->prior_log_vars, a->K, a->D, w, ws);
     if (rc) return rc;
-    {   // the prior-table operands ride as Kp extra workgroups of the row kernel
-        ProfScope ps(s, "vade_pre", 0.0, 4.0 * (BD * (2.0 + (a->eps ? 1.0 : 0.0) + 4.0 + 2.0 + 1.0)) + 16.0 * a->K * a->D);
-        DMVAE_LAUNCH(vade_pre_kernel, dim3(nrb + w.Kp), dim3(256), 0, s, L, nrb);
-    }
-    rc = check_launch("vade_pre");
+    // the prior-table operands ride as Kp extra workgroups of the row kernel
+    rc = latent_launch_rows(s, "vade_pre", 4.0 * (BD * (2.0 + (a->eps ? 1.0 : 0.0) + 4.0 + 2.0 + 1.0)) + 16.0 * a->K * a->D, vade_pre_kernel, nrb + w.Kp, L, nrb);
     if (rc) return rc;
     {
         ProfScope ps(s, "vade_gemm_f32", 2.0 * Bp2 * (double)w.Kp * 2.0 * w.Dp, 4.0 * Bp2 * (2.0 * w.Dp + (double)w.nsplit_s * w.Kp));
         rc = vade_score_gemm(s, w, ws, Bp2);
     }
     if (rc) return rc;
-    {
-        ProfScope ps(s, "vade_rows", 0.0, 4.0 * BK * (4.0 * w.nsplit_s + 3.0));
-        DMVAE_LAUNCH(vade_rows_kernel, dim3(nrb), dim3(256), 0, s, L);
-    }
-    rc = check_launch("vade_rows");
+    rc = latent_launch_rows(s, "vade_rows", 4.0 * BK * (4.0 * w.nsplit_s + 3.0), vade_rows_kernel, nrb, L);
     if (rc) return rc;
     {
         ProfScope ps(s, "vade_gemm_f32", 2.0 * Bp2 * (double)w.Kp * (2.0 * w.Dp + w.XW), 4.0 * Bp2 * (2.0 * w.Kp + w.XW + 2.0 * w.Dp));
@@ -462,12 +361,8 @@ int latent_vade_mfma_launch(hipStream_t s, const dmvae_latent_args* a, float* ws
         rc = gemm_f32_trio(s, g1, 1, none, 1, g3, 2 * w.nsplit);
     }
     if (rc) return rc;
-    {
-        const int extra = (int)std::min<int64_t>(256, ((int64_t)a->K * a->D + 255) / 256);
-        ProfScope ps(s, "vade_post", 0.0, 4.0 * (BD * (4.0 + 2.0 + 2.0 + 2.0)) + 8.0 * w.nsplit * w.Kp * w.XW);
-        DMVAE_LAUNCH(vade_post_kernel, dim3(nrb + extra), dim3(256), 0, s, L, nrb);
-    }
-    return check_launch("vade_post");
+    return latent_launch_rows(s, "vade_post", 4.0 * (BD * (4.0 + 2.0 + 2.0 + 2.0)) + 8.0 * w.nsplit * w.Kp * w.XW, vade_post_kernel,
+                              nrb + prior_grad_workgroups(a->K, a->D), L, nrb);
 }
 
 // ---- evaluation: averaged responsibilities of `draws` samples (eval_clusters.hip), the forward half per draw
@@ -494,33 +389,20 @@ __global__ __launch_bounds__(256) void vade_eval_z_kernel(VadeEvalMfma L, int j)
     const bool vec = D % 4 == 0 && a.ld_mean % 4 == 0 && a.ld_log_var % 4 == 0 && (!a.eps || a.ld_eps % 4 == 0) &&
                      ((reinterpret_cast<uintptr_t>(a.mean) | reinterpret_cast<uintptr_t>(a.log_var) | reinterpret_cast<uintptr_t>(a.eps)) & 15) == 0;
     for (int d0 = 4 * lane16; d0 < Dp; d0 += 64) {
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (valid && d0 < D) {
-            float mu[4], lv[4], ep[4];
-            if (vec) {
-                const float4 m4 = *reinterpret_cast<const float4*>(mrow + d0), l4 = *reinterpret_cast<const float4*>(vrow + d0);
-                mu[0] = m4.x; mu[1] = m4.y; mu[2] = m4.z; mu[3] = m4.w;
-                lv[0] = l4.x; lv[1] = l4.y; lv[2] = l4.z; lv[3] = l4.w;
-                if (erow) {
-                    const float4 e4 = *reinterpret_cast<const float4*>(erow + d0);
-                    ep[0] = e4.x; ep[1] = e4.y; ep[2] = e4.z; ep[3] = e4.w;
-                }
-            } else {
+        float mu[4], lv[4], ep[4];
+        load_quad(mrow, vrow, erow, vec, d0, D, mu, lv, ep);
+        const bool ok[4] = {valid && d0 < D, valid && d0 + 1 < D, valid && d0 + 2 < D, valid && d0 + 3 < D};
+        if (ok[0] && !erow) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int off = d0 + i < D ? d0 + i : 0;
-                    mu[i] = mrow[off]; lv[i] = vrow[off];
-                    if (erow) ep[i] = erow[off];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (!erow) ep[i] = philox_normal_at(a.seed, a.counter, EVAL_PHILOX_STREAM, ((uint64_t)j * (uint64_t)a.rows.n_rows + pos) * (uint64_t)D + (d0 + i < D ? d0 + i : 0));
-                z[i] = d0 + i < D ? mu[i] + __expf(0.5f * lv[i]) * ep[i] - L.ws[L.w.m0 + d0 + i] : 0.f;      // from the tables' origin
-            }
+            for (int i = 0; i < 4; ++i)
+                ep[i] = philox_normal_at(a.seed, a.counter, EVAL_PHILOX_STREAM, ((uint64_t)j * (uint64_t)a.rows.n_rows + pos) * (uint64_t)D + (d0 + i < D ? d0 + i : 0));
         }
-        *reinterpret_cast<float4*>(Xz + d0) = make_float4(z[0] * z[0], z[1] * z[1], z[2] * z[2], z[3] * z[3]);
-        *reinterpret_cast<float4*>(Xz + Dp + d0) = make_float4(z[0], z[1], z[2], z[3]);
+        const float4 o4 = *reinterpret_cast<const float4*>(L.ws + L.w.m0 + d0);      // from the tables' origin
+        const float org[4] = {o4.x, o4.y, o4.z, o4.w};
+        float z[4], cl[4], x1[4], zs[4], lvsum = 0.f;
+        reparam_quad(mu, lv, ep, ok, org, z, cl, x1, zs, lvsum);      // (only zs is used)
+        *reinterpret_cast<float4*>(Xz + d0) = make_float4(zs[0] * zs[0], zs[1] * zs[1], zs[2] * zs[2], zs[3] * zs[3]);
+        *reinterpret_cast<float4*>(Xz + Dp + d0) = make_float4(zs[0], zs[1], zs[2], zs[3]);
     }
 }
 
@@ -547,8 +429,7 @@ __global__ __launch_bounds__(256) void vade_eval_rows_kernel(VadeEvalMfma L, int
         for (int i = 0; i < 4; ++i)
             if (k0 + i < K) mxd = fmax(mxd, -0.5 * uz[i]);
     }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) mxd = fmax(mxd, __shfl_xor(mxd, o, 16));
+    mxd = row_max16(mxd);
     float se = 0.f;
     for (int k0 = 4 * lane16; k0 < K; k0 += 64) {
         double uz[4];
@@ -582,34 +463,18 @@ int vade_eval_mfma_launch(hipStream_t s, const VadeEvalArgs& a) {
     L.a = a; L.w = w; L.ws = a.ws;
     const int nrb = a.B_pad / 16;
     const double n = a.rows.n_valid;
-    {
-        ProfScope ps(s, "vade_origin", 0.0, 16.0 * a.K * a.D);
-        DMVAE_LAUNCH(vade_origin_kernel, dim3((w.Dp + 255) / 256), dim3(256), 0, s, a.prior_means, a.prior_log_vars, a.K, a.D, w.Dp, a.ws + w.m0);
-    }
-    int rc = check_launch("vade_origin");
+    int rc = vade_origin_launch(s, a.prior_means, a.prior_log_vars, a.K, a.D, w, a.ws);
     if (rc) return rc;
-    {
-        ProfScope ps(s, "vade_tables", 0.0, 24.0 * a.K * a.D);
-        DMVAE_LAUNCH(vade_tables_kernel, dim3(w.Kp), dim3(256), 0, s, a.prior_means, a.prior_log_vars, a.K, a.D, w, a.ws);
-    }
-    rc = check_launch("vade_tables");
+    rc = latent_launch_rows(s, "vade_tables", 24.0 * a.K * a.D, vade_tables_kernel, w.Kp, a.prior_means, a.prior_log_vars, a.K, a.D, w, a.ws);
     if (rc) return rc;
     for (int j = 0; j < a.draws; ++j) {
-        {
-            ProfScope ps(s, "vade_eval_z", 0.0, 4.0 * n * a.D * (4.0 + (a.eps ? 1.0 : 0.0)));
-            DMVAE_LAUNCH(vade_eval_z_kernel, dim3(nrb), dim3(256), 0, s, L, j);
-        }
-        if ((rc = check_launch("vade_eval_z"))) return rc;
+        if ((rc = latent_launch_rows(s, "vade_eval_z", 4.0 * n * a.D * (4.0 + (a.eps ? 1.0 : 0.0)), vade_eval_z_kernel, nrb, L, j))) return rc;
         {
             ProfScope ps(s, "vade_gemm_f32", 2.0 * a.B_pad * (double)w.Kp * 2.0 * w.Dp, 4.0 * a.B_pad * (2.0 * w.Dp + (double)w.nsplit_s * w.Kp));
             rc = vade_score_gemm(s, w, a.ws, a.B_pad);
         }
         if (rc) return rc;
-        {
-            ProfScope ps(s, "vade_eval_rows", 0.0, 4.0 * n * a.K * (2.0 * w.nsplit_s + 4.0));
-            DMVAE_LAUNCH(vade_eval_rows_kernel, dim3(nrb), dim3(256), 0, s, L, j);
-        }
-        if ((rc = check_launch("vade_eval_rows"))) return rc;
+        if ((rc = latent_launch_rows(s, "vade_eval_rows", 4.0 * n * a.K * (2.0 * w.nsplit_s + 4.0), vade_eval_rows_kernel, nrb, L, j))) return rc;
     }
     return confusion_add_launch(s, a.w, a.ld_w, a.K, a.rows);      // the same arg-max and count as vade_eval_kernel's
 }

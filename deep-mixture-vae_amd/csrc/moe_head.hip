@@ -13,7 +13,7 @@
 //     dP (act dtype: the weight-gradient operand; f32 in place of P), dlogits += q (dq - sum q dq) (NOT scaled by kl_ratio),
 //     featLearn: inp_act = relu(mean) (the weight-gradient operand) and gmu += (dP . W^T) * [mean > 0].
 //
-// Layout: 64-thread workgroups, 16 lanes per row (row_sum16 of latent_body.h): lane l owns the outputs o = l, l + 16, l + 32,
+// Layout: 64-thread workgroups, 16 lanes per row (row_sum16 of common.h): lane l owns the outputs o = l, l + 16, l + 32,
 // l + 48 (O <= 64) of its row and walks the experts; the per-expert softmax reductions over o are 16-lane shuffles.  Y is read
 // through the batch permutation (row r of the batch = Y[perm[first + r]], first = state->batch_cursor * batch when the device
 // cursor is used), as the reconstruction epilogue reads its targets.  Per-workgroup loss / error partials go to partials[blk][2]

@@ -294,7 +294,8 @@ def test_gemm_rejects_unaligned_shapes(hip):
 
 
 # ------------------------------------------------------------------ latent kernel
-def run_latent(L, mean, log_var, logits, eps, gumbel, pm, plv, mode, tau, kl_ratio, act_dtype, B_pad=None, ldpad=0, mfma=False, seed=1234, noise_step=7):
+def run_latent(L, mean, log_var, logits, eps, gumbel, pm, plv, mode, tau, kl_ratio, act_dtype, B_pad=None, ldpad=0, mfma=False, seed=1234, noise_step=7,
+               ldZ=None):
     B, D = mean.shape
     K = logits.shape[1]
     B_pad = B_pad or ((B + 63) // 64 * 64)
@@ -309,14 +310,15 @@ def run_latent(L, mean, log_var, logits, eps, gumbel, pm, plv, mode, tau, kl_rat
     gd = dev(gumbel) if gumbel is not None else None
     pmd, plvd = dev(pm), dev(plv)
     adt = torch.bfloat16 if act_dtype == 1 else torch.float32
-    ldZ = (D + 63) // 64 * 64
+    ldg = (D + 63) // 64 * 64
+    ldZ = ldZ or ldg                 # (ldZ: a Z buffer wider than D padded to 64)
     ldl = (K + 63) // 64 * 64
     Z = torch.full((B_pad, ldZ), 9.0, dtype=adt, device="cuda")
     Zf = torch.zeros((B_pad, D), dtype=torch.float32, device="cuda")
     w = torch.zeros((B_pad, K), dtype=torch.float32, device="cuda")
-    gmu = torch.full((B_pad, ldZ), 9.0, dtype=torch.float32, device="cuda")
-    glv = torch.full((B_pad, ldZ), 9.0, dtype=torch.float32, device="cuda")
-    clv = torch.full((B_pad, ldZ), 9.0, dtype=torch.float32, device="cuda")
+    gmu = torch.full((B_pad, ldg), 9.0, dtype=torch.float32, device="cuda")
+    glv = torch.full((B_pad, ldg), 9.0, dtype=torch.float32, device="cuda")
+    clv = torch.full((B_pad, ldg), 9.0, dtype=torch.float32, device="cuda")
     dlg = torch.full((B_pad, ldl), 9.0, dtype=adt, device="cuda")
     nblk = L.lib.dmvae_latent_nblocks(B_pad, D, K)
     dpri = torch.zeros((nblk, 2 * K * D), dtype=torch.float32, device="cuda")
@@ -335,7 +337,7 @@ def run_latent(L, mean, log_var, logits, eps, gumbel, pm, plv, mode, tau, kl_rat
     a.Z_act, a.ld_Z = L.ptr(Z).value, ldZ
     a.Z_f32, a.ld_Zf = L.ptr(Zf).value, D
     a.weights, a.ld_w = L.ptr(w).value, K
-    a.gmu, a.glv, a.clv, a.ld_g = L.ptr(gmu).value, L.ptr(glv).value, L.ptr(clv).value, ldZ
+    a.gmu, a.glv, a.clv, a.ld_g = L.ptr(gmu).value, L.ptr(glv).value, L.ptr(clv).value, ldg
     a.dlogits_act, a.ld_dl = L.ptr(dlg).value, ldl
     a.dprior_partials, a.loss_partials = L.ptr(dpri).value, L.ptr(lp).value
     if mfma:          # the MFMA form of the contractions (csrc/latent_mfma.hip): the caller brings the scratch
@@ -444,6 +446,41 @@ def test_latent_mfma_form_matches_oracle(hip, shape, noise):
         c = run_latent(L, mean, lv, logits, eps, None, pm, plv, 0, 1.0, 0.6, 0, ldpad=4)
         assert g["klz"] == pytest.approx(c["klz"], rel=2e-5)
         np.testing.assert_allclose(g["dlogits"][:B, :K], c["dlogits"][:B, :K], rtol=1e-3, atol=1e-4 * sc)
+
+
+def _mfma_latent_inputs(B, D, K):
+    rng = np.random.RandomState(B + D + K)
+    f32 = lambda a: a.astype(np.float32).astype(np.float64)
+    return dict(mean=f32(rng.randn(B, D) * 1.2), lv=f32(rng.randn(B, D) * 0.5 - 0.2), logits=f32(rng.randn(B, K) * 1.5), eps=f32(rng.randn(B, D)),
+                pm=f32(rng.randn(K, D)), plv=f32(rng.randn(K, D) * 0.4))
+
+
+@pytest.mark.parametrize("shape,ldpad", [((128, 256, 50), 0), ((333, 30, 200), 4)])
+@pytest.mark.parametrize("noise", ["caller", "device"])
+def test_latent_mfma_bf16_Z_is_the_rounded_f32_Z(hip, shape, ldpad, noise):
+    """The bf16 Z of the MFMA form: Z[:B, :D] is Z_f32 rounded to nearest even, bit for bit (the hardware convert of common.h's f2bf / pack2bf
+    is that rounding), and every other element of Z -- pad columns, pad rows -- is zero.  (128, 256, 50): the aligned path, two bf16 packed per
+    32-bit word, four per store; (333, 30, 200) with padded leading dimensions: the element-by-element path."""
+    B, D, K = shape
+    i = _mfma_latent_inputs(B, D, K)
+    g = run_latent(hip, i["mean"], i["lv"], i["logits"], i["eps"] if noise == "caller" else None, None, i["pm"], i["plv"], 0, 1.0, 0.6, 1, ldpad=ldpad, mfma=True)
+    want = torch.from_numpy(g["Zf"][:B]).bfloat16().float().numpy()
+    assert np.abs(g["Zf"][:B]).max() > 1.0                      # (something was drawn and written)
+    np.testing.assert_array_equal(g["Z"][:B, :D], want)
+    assert not g["Z"][:, D:].any() and not g["Z"][B:].any()
+
+
+@pytest.mark.parametrize("act_dtype", [0, 1])
+def test_latent_mfma_Z_buffer_wider_than_padded_D(hip, act_dtype):
+    """ld_Z = Dp + 64: columns [D, ld_Z) of every row come back zero (they are K padding of the decoder's first GEMM) and Z[:B, :D] is what
+    the ld_Z = Dp run writes."""
+    B, D, K = 64, 64, 64
+    i = _mfma_latent_inputs(B, D, K)
+    run = lambda ldZ: run_latent(hip, i["mean"], i["lv"], i["logits"], i["eps"], None, i["pm"], i["plv"], 0, 1.0, 0.6, act_dtype, mfma=True, ldZ=ldZ)
+    narrow, wide = run(None), run(64 + 64)
+    assert wide["Z"].shape == (64, 128) and np.abs(narrow["Z"][:B, :D]).max() > 1.0
+    assert not wide["Z"][:, D:].any()
+    np.testing.assert_array_equal(wide["Z"][:B, :D], narrow["Z"][:B, :D])
 
 
 def test_latent_fwd_against_reference_golden_vectors(hip, golden):

@@ -22,10 +22,11 @@ import vade_large as V      # noqa: E402
 KNOB_FORCE_LARGE = 22
 
 
-def run_stage(c, forced=False, scratch=True, noise=None):
+def run_stage(c, forced=False, scratch=True, noise=None, act_dtype=None, ldZ=None):
     """dmvae_latent_fwd mode 2 exactly as tests/test_gpu_vade.py::test_vade_latent_stage_matches_oracle drives it, every output
     requested, plus the scratch of the large-table form where the shape (or the knob) asks for it.  noise = (seed, step): the
-    device draws eps instead of taking c["eps"]"""
+    device draws eps instead of taking c["eps"].  act_dtype (default: f32 and no f32 copy): Z in that dtype and the f32 copy Zf
+    beside it; ldZ (default: D padded to 64): the leading dimension of Z"""
     from dmvae_hip import lib, _lib
     B, D, K = c["B"], c["D"], c["K"]
     Bp, ldD = (B + 63) // 64 * 64, (D + 63) // 64 * 64
@@ -33,12 +34,16 @@ def run_stage(c, forced=False, scratch=True, noise=None):
     md, lvd = dev(c["mean"], ldD), dev(c["lv"], ldD)
     epsd = torch.as_tensor(c["eps"].astype(np.float32)).cuda()
     pmd, plvd = torch.as_tensor(c["pm"].astype(np.float32)).cuda(), torch.as_tensor(c["plv"].astype(np.float32)).cuda()
-    Z = torch.full((Bp, ldD), 9.0, device="cuda"); w = torch.zeros((Bp, K), device="cuda")
+    ldZ = ldZ or ldD
+    Z = torch.full((Bp, ldZ), 9.0, device="cuda", dtype=torch.bfloat16 if act_dtype == _lib.BF16 else torch.float32); w = torch.zeros((Bp, K), device="cuda")
+    Zf = torch.zeros((Bp, D), device="cuda") if act_dtype is not None else None
     gmu, glv, clv = (torch.zeros((Bp, ldD), device="cuda") for _ in range(3))
     nblk = lib.dmvae_latent_nblocks_vade(Bp)
     dpri, lp = torch.zeros((nblk, 2 * K * D), device="cuda"), torch.zeros((nblk, 2), device="cuda")
     la = _lib.LatentArgs()
-    la.B, la.B_pad, la.D, la.K, la.mode, la.act_dtype = B, Bp, D, K, 2, _lib.F32
+    la.B, la.B_pad, la.D, la.K, la.mode, la.act_dtype = B, Bp, D, K, 2, _lib.F32 if act_dtype is None else act_dtype
+    if Zf is not None:
+        la.Z_f32, la.ld_Zf = Zf.data_ptr(), D
     la.kl_ratio, la.temperature, la.inv_B = c["kl_ratio"], 1.0, 1.0 / B
     la.mean, la.ld_mean, la.log_var, la.ld_log_var = md.data_ptr(), ldD, lvd.data_ptr(), ldD
     if noise is None:
@@ -46,7 +51,7 @@ def run_stage(c, forced=False, scratch=True, noise=None):
     else:
         la.seed, la.noise_step = noise
     la.prior_means, la.prior_log_vars = pmd.data_ptr(), plvd.data_ptr()
-    la.Z_act, la.ld_Z, la.weights, la.ld_w = Z.data_ptr(), ldD, w.data_ptr(), K
+    la.Z_act, la.ld_Z, la.weights, la.ld_w = Z.data_ptr(), ldZ, w.data_ptr(), K
     la.gmu, la.glv, la.clv, la.ld_g = gmu.data_ptr(), glv.data_ptr(), clv.data_ptr(), ldD
     la.dprior_partials, la.loss_partials = dpri.data_ptr(), lp.data_ptr()
     nb = int(lib.dmvae_latent_vade_ws_bytes(Bp, D, K, 1 if forced else 0, None)) if scratch else 0
@@ -61,7 +66,7 @@ def run_stage(c, forced=False, scratch=True, noise=None):
     finally:
         if forced:
             _lib.check(lib.dmvae_debug_set_knob(KNOB_FORCE_LARGE, 0), "knob")
-    return dict(Z=Z, w=w, gmu=gmu, glv=glv, clv=clv, dpri=dpri, lp=lp, ws_bytes=nb)
+    return dict(Z=Z, Zf=Zf, w=w, gmu=gmu, glv=glv, clv=clv, dpri=dpri, lp=lp, ws_bytes=nb)
 
 
 def check_stage(o, c, want):
@@ -139,6 +144,32 @@ def test_large_table_form_draws_what_the_table_says(shape, forced):
 
 
 # ---------------------------------------------------------------------------------------------------------------- (b)
+@pytest.mark.parametrize("shape,forced", [((93, 256, 10), False), ((70, 33, 3), True)])
+@pytest.mark.parametrize("noise", [None, (1234, 7)])
+def test_large_table_form_bf16_Z_is_the_rounded_f32_Z(shape, forced, noise):
+    """Z[:B, :D] in bf16 is Z_f32 rounded to nearest even, bit for bit (csrc/common.h's f2bf / pack2bf are the hardware convert: that
+    rounding); every other element of Z is zero.  D = 256: the packed store; D = 33: element by element, a quad that straddles D."""
+    from dmvae_hip import _lib
+    B, D, K = shape
+    o = run_stage(V.latent_case(B, D, K, scaled=not forced), forced=forced, noise=noise, act_dtype=_lib.BF16)
+    assert o["ws_bytes"] > 0 and o["Zf"][:B].abs().max() > 1.0
+    assert torch.equal(o["Z"][:B, :D], o["Zf"][:B].bfloat16())
+    assert not o["Z"][:, D:].any() and not o["Z"][B:].any()
+
+
+@pytest.mark.parametrize("act", ["F32", "BF16"])
+def test_large_table_form_Z_buffer_wider_than_padded_D(act):
+    """ld_Z = Dp + 64: columns [D, ld_Z) of every row come back zero, Z[:B, :D] is what the ld_Z = Dp run writes"""
+    from dmvae_hip import _lib
+    B, D, K = 64, 33, 3
+    c = V.latent_case(B, D, K, scaled=False)
+    narrow = run_stage(c, forced=True, act_dtype=getattr(_lib, act))
+    wide = run_stage(c, forced=True, act_dtype=getattr(_lib, act), ldZ=64 + 64)
+    assert wide["ws_bytes"] > 0 and wide["Z"].shape == (64, 128) and narrow["Z"][:B, :D].float().abs().max() > 1.0
+    assert not wide["Z"][:, D:].any()
+    assert torch.equal(wide["Z"][:B, :D], narrow["Z"][:B, :D])
+
+
 @pytest.mark.parametrize("shape", [(100, 64, 20), (70, 33, 3)])
 def test_both_forms_agree_where_both_run(shape):
     c = V.latent_case(*shape, scaled=False)
