@@ -415,6 +415,55 @@ class DeepMixtureVAE(VAE):
             eng.eval_loglik(acc, n, N, s, k, counter=counter)
         return eng.read_loglik(acc)[0]
 
+    _metrics_draws = 1                                     # get_cluster_metrics: the draws eval_clusters averages (VaDE: 10)
+
+    def get_cluster_metrics(self, session, data, silhouette=True, counter=0, return_labels=False):
+        """Cluster quality beside the accuracy: dict(acc, nmi, ari, purity, silhouette, n_clusters_used) of `data` (dmvae_hip.metrics).
+        acc / nmi / ari / purity come from the confusion matrix [cluster][class] that get_accuracy(eval="device") builds; silhouette
+        is the label-free coefficient of the encoder means under the arg-max labels, all pairs on the GPU (csrc/cluster_metrics.hip),
+        nan with fewer than 2 (or with n) non-empty clusters.  Walks the data set in its current order WITHOUT reshuffling and draws
+        nothing from the NumPy stream; VaDE's responsibilities use the device Philox noise (stream 2, `counter`, 10 draws) whatever
+        noise= says.  The loop only enqueues -- gather, encoder and count, the labels, a device copy of the means -- then one
+        silhouette call; the matrix, its flag, two doubles and the silhouette's flag come back at the end.  Works with either
+        eval= setting.  return_labels: (the dict, the int32 labels of the rows in the evaluated order) instead."""
+        return self._cluster_metrics(data, self.n_classes, silhouette, counter, return_labels)
+
+    def _cluster_metrics(self, data, R, silhouette, counter, return_labels):
+        import torch
+        from dmvae_hip import metrics
+        eng, dev = self._engine, self._session.device
+        rows, cls = data.device_rows(dev), data.device_classes(dev)
+        order = data.order
+        t = torch.as_tensor(np.ascontiguousarray(order, dtype=np.int32))
+        if self._eval_perm is None or self._eval_perm.numel() != t.numel():
+            self._eval_perm = torch.empty(t.numel(), dtype=torch.int32, device=dev)
+        self._eval_perm.copy_(t)
+        conf = eng.confusion_buffer(R, dev)
+        b, N, D = eng.max_batch, len(order), self.latent_dim
+        silhouette = bool(silhouette) and N >= 2
+        labels = torch.empty(N, dtype=torch.int32, device=dev)
+        Z = torch.empty((N, D), dtype=torch.float32, device=dev) if silhouette else None
+        for s in range(0, N, b):
+            n = min(b, N - s)
+            eng.load_batch(rows, self._eval_perm, s, n)
+            eng.eval_clusters(conf, cls, self._eval_perm, s, n, draws=self._metrics_draws, eps=None, counter=counter)
+            eng.eval_labels(labels[s:s + n], n)
+            if silhouette:
+                Z[s:s + n].copy_(eng.view("mean", n))
+        if silhouette:
+            _, out, flag = metrics.silhouette_enqueue(Z, labels, self.n_classes)
+        d = eng.read_confusion(conf)
+        res = metrics.scores_from_confusion(d)
+        res["silhouette"] = float("nan")
+        res["n_clusters_used"] = int((d.sum(axis=1) > 0).sum())
+        if silhouette:
+            total, used = out.cpu().tolist()
+            if int(flag.item()):
+                raise IndexError("cluster metrics on the device: a label outside [0, %d)" % self.n_classes)
+            if 2 <= int(used) <= N - 1:
+                res["silhouette"] = total / N
+        return (res, labels.cpu().numpy()) if return_labels else res
+
     # ------------------------------------------------------------------ pretraining (base_models.py:304-423)
     # the variables tf.get_collection(TRAINABLE_VARIABLES, scope=name + "/encoder_network/c") returns (:313-315)
     PRIOR_VAR_LIST = ("W_ch", "b_ch", "W_logits", "b_logits")
@@ -590,6 +639,8 @@ class VaDE(DeepMixtureVAE):
     cnn=True (:456-488): the batch as 28x28x1 images through the same six-convolution / three-pool stack as DMVAE's
     checked-in encoder, ending in ("fc", 2048 -> 128), with mean / log_var straight off those 128 units
     (dmvae_config.trunk = DMVAE_TRUNK_CNN, enc = (128,))."""
+
+    _metrics_draws = 10                                     # get_cluster_metrics: get_accuracy's default k
 
     def __init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=None, initializer=None, cnn=False, *,
                  batch_size=100, dtype="bf16", enc_layers=(2000, 500, 500), dec_layers=(500, 500, 2000), noise="device", seed=0,

@@ -17,6 +17,7 @@
 #include "eval_clusters.h"
 #include "eval_loglik.h"
 #include "tsne.h"
+#include "cluster_metrics.h"
 #include "measure.h"
 
 namespace dmvae {
@@ -1589,6 +1590,14 @@ extern "C" const float* dmvae_tsne_p(const void* ws) { return (const float*)ws; 
 extern "C" int dmvae_confusion_add(void* stream, const float* scores, int64_t ld, int n_valid, int K, const int32_t* classes, int64_t n_rows,
                                    const int32_t* perm, int64_t first, int32_t* conf, int R, int32_t* err_flag) {
     return confusion_add_launch((hipStream_t)stream, scores, ld, K, EvalRows{classes, n_rows, perm, first, n_valid, conf, R, err_flag});
+}
+extern "C" int dmvae_argmax_labels(void* stream, const float* scores, int64_t ld, int n_valid, int K, int32_t* labels) {
+    return argmax_labels_launch((hipStream_t)stream, scores, ld, n_valid, K, labels);
+}
+extern "C" int64_t dmvae_silhouette_ws_bytes(int64_t n, int K) { return silhouette_ws_bytes(n, K); }
+extern "C" int dmvae_silhouette(void* stream, const float* Z, int64_t ldz, int n, int D, const int32_t* labels, int K, void* ws, int64_t ws_bytes,
+                                float* samples, double* out, int32_t* err_flag) {
+    return silhouette_launch((hipStream_t)stream, Z, ldz, n, D, labels, K, ws, ws_bytes, samples, out, err_flag);
 }
 extern "C" int dmvae_recon_nblocks(int B_pad, int I_pad) { return recon_nblocks(B_pad, I_pad); }
 extern "C" int dmvae_recon_fwd_bwd(void* stream, int act_dtype, int recon_kind, int B, int B_pad, int I, int I_pad, const float* logits,

@@ -21,32 +21,13 @@
 // nothing and sets a bit of the error flag.  Rows >= n_valid count nothing and are not launched.
 #include "latent_body.h"
 #include "eval_clusters.h"
+#include "row_argmax.h"
 
 namespace dmvae {
 
 constexpr int EVAL_RB = 16;        // rows per workgroup
 
-// First index of the largest of s[0 .. K): the lane walks k = lane + 16 i in ascending order (strict >: the first of
-// equal values within the lane), then the 16 lanes are combined, equal values going to the smaller index.  Every lane
-// of the row returns the index.  K = 0 (a row that is not there): no load, the result is not used.  NaN scores are
-// not ordered: the scores must not hold any.
-template <typename P>
-__device__ __forceinline__ int row_argmax16(P s, int K, int lane) {
-    float bv = -INFINITY;
-    int bi = 1 << 30;
-    if (lane < K) { bv = s[lane]; bi = lane; }
-    for (int k = lane + 16; k < K; k += 16) {
-        const float v = s[k];
-        if (v > bv) { bv = v; bi = k; }
-    }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 16);
-        const int oi = __shfl_xor(bi, o, 16);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    return bi;
-}
+// (row_argmax16: row_argmax.h)
 
 // one lane per row; 0 <= first and first + n_valid <= n_rows were checked on the host, cluster < K <= R
 __device__ __forceinline__ void eval_count(const EvalRows& r, int b, int cluster) {

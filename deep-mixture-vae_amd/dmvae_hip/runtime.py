@@ -634,6 +634,14 @@ class StepEngine:
                 m for bit, m in ((1, "a class outside [0, %d)" % R), (2, "a permutation entry outside the data set")) if host[-1] & bit))
         return host[:-1].reshape(R, R).astype(np.int64)
 
+    def eval_labels(self, out, n_valid=None):
+        """dmvae_argmax_labels on the scores eval_clusters has just left for the loaded batch -- the "logits" view (DMVAE plans), the
+        "eval_w" view (VaDE plans: the averaged responsibilities) -- into out, int32 [n_valid] on the device: the cluster of every row,
+        by the rule the confusion matrix was counted with.  Only enqueues."""
+        from . import metrics
+        n_valid = self.max_batch if n_valid is None else int(n_valid)
+        return metrics.argmax_labels(self.view("eval_w" if self.model == "vade" else "logits", n_valid), out=out)
+
     # ------------------------------------------------------------ held-out log-likelihood on the device
     def loglik_buffer(self):
         """a zeroed float64 [2] device buffer: [sum of the rows' log-likelihood bounds, rows] (eval_loglik adds into it)"""

@@ -183,6 +183,12 @@ class MoE:
             return 1 - error / data.len, acc_cl
         return -error / data.epoch_len, acc_cl
 
+    def get_cluster_metrics(self, session, data, silhouette=True, counter=0, return_labels=False):
+        """The gate's cluster quality (DeepMixtureVAE.get_cluster_metrics): dict(acc, nmi, ari, purity, silhouette, n_clusters_used)
+        of the experts' arg-max against the classes, the matrix sized max(E, n_classes) as get_accuracy sizes it.  No reshuffle."""
+        n_classes = int(np.max(data._cls)) + 1
+        return self.vae._cluster_metrics(data, max(self.n_experts, n_classes), silhouette, counter, return_labels)
+
     def predict(self, X):
         """(reconstructed_Y, reconstructed_Y_soft) of models.py:83-108 for the rows X (regression: the prediction twice)"""
         import torch

@@ -15,6 +15,7 @@ New flags (defaults = reference behaviour): --batch_size, --dtype, --seed,
 --gmm, --gmm_seeding (host | device: where --gmm device draws its k-means++ centres),
 --eval (host | device: where get_accuracy takes its arg-max and confusion matrix),
 --loglik S (dmvae / vade: held-out log-likelihood of the test set per epoch, the importance-weighted bound with S draws; 0 = off),
+--metrics (per epoch: NMI, ARI, purity and the silhouette coefficient of the test set's latent means beside the accuracy, get_cluster_metrics),
 --tsne (off | host | device: with --plotting, sampled.png gains the t-SNE scatter of the prior samples, embedded by sklearn on the CPU or by
 the exact t-SNE in HIP, dmvae_hip.tsne.TSNE).
 """
@@ -91,11 +92,21 @@ parser.add_argument("--eval", type=str, default="host", choices=["host", "device
 parser.add_argument("--loglik", type=int, default=0,
                     help="dmvae / vade: S > 0 adds llTest to the epoch line -- the test set's log-likelihood in nats per row, the importance-weighted "
                          "bound with S draws computed on the device (get_log_likelihood); 0 = off")
+parser.add_argument("--metrics", action="store_true", default=False,
+                    help="per epoch, beside the accuracy: NMI, ARI and purity of the test set's clusters against its classes and the silhouette "
+                         "coefficient of its latent means, computed on the device (get_cluster_metrics); adds nmiTest / silTest to the epoch line")
 parser.add_argument("--tsne", type=str, default="off", choices=["off", "host", "device"],
                     help="--plotting: add the t-SNE scatter of the prior samples (1000 per cluster) to sampled.png, embedded with sklearn on the "
                          "host (the reference's call) or with the exact t-SNE on the device (dmvae_hip.tsne.TSNE); off = the sample grid alone")
 parser.add_argument("--cnn", action="store_true", default=False,
                     help="the checked-in convolutional encoder trunk (base_models.py:156,176-216) instead of the MLP branch")
+
+
+def _metrics_record(cm):
+    """the JSONL keys of --metrics (a silhouette that is not defined -- fewer than two clusters in use -- is written as null)"""
+    sil = float(cm["silhouette"])
+    return dict(nmi_test=float(cm["nmi"]), ari_test=float(cm["ari"]), purity_test=float(cm["purity"]),
+                silhouette_test=None if math.isnan(sil) else sil, clusters_used_test=int(cm["n_clusters_used"]))
 
 
 def main(argv):
@@ -207,6 +218,7 @@ def main(argv):
             accTest = model.get_accuracy(sess, test_data)
             eval_seconds = time.perf_counter() - t_eval
             llTest = model.get_log_likelihood(sess, test_data, k=argv.loglik, counter=epoch) if argv.loglik > 0 else None
+            cmTest = model.get_cluster_metrics(sess, test_data, counter=epoch) if argv.metrics else None
             improved = accTest > maxAcc
             if world > 1:
                 # the branch below holds a COLLECTIVE (sync_master): rank 0 decides and every rank follows.  Each rank scores the same
@@ -235,6 +247,8 @@ def main(argv):
                            eval_seconds=eval_seconds, eval=argv.eval, world=world, batch_size=argv.batch_size, dtype=argv.dtype, model=model_str)
                 if llTest is not None:
                     rec.update(ll_test=float(llTest), loglik_draws=argv.loglik)
+                if cmTest is not None:
+                    rec.update(_metrics_record(cmTest))
                 with open(argv.model + "_metrics.jsonl", "a") as fl:
                     fl.write(json.dumps(rec) + "\n")
             if math.isnan(loss):
@@ -243,6 +257,8 @@ def main(argv):
                        "maxAcc": "%.4f" % maxAcc, "accClusteringTest": "%.4f" % accTest}
             if llTest is not None:
                 postfix["llTest"] = "%.4f" % llTest
+            if cmTest is not None:
+                postfix.update(nmiTest="%.4f" % cmTest["nmi"], silTest="%.4f" % cmTest["silhouette"])
             bar.set_postfix(postfix)
     if plotting:                                                  # train.py:332-334
         visualization.mnist_sample_plot(model, sess, tsne=argv.tsne != "off", tsne_backend=argv.tsne if argv.tsne != "off" else "host")
@@ -306,6 +322,7 @@ def main_moe(argv, world, rank):
         accTrain, accClTrain = model.get_accuracy(sess, train_data)
         accTest, accClTest = model.get_accuracy(sess, test_data)
         eval_seconds = time.perf_counter() - t_eval
+        cmTest = model.get_cluster_metrics(sess, test_data, counter=epoch) if argv.metrics else None
         if accTest > maxAcc:
             maxAcc = accTest
             with open(ckpt_path + ".tmp", "wb") as f:
@@ -315,6 +332,8 @@ def main_moe(argv, world, rank):
                    acc_test=float(accTest), acc_clustering_train=float(accClTrain), acc_clustering_test=float(accClTest),
                    max_acc=float(maxAcc), kl_ratio=float(anneal_term), eval_seconds=eval_seconds, eval=argv.eval, batch_size=argv.batch_size,
                    dtype=argv.dtype, model=argv.model)
+        if cmTest is not None:
+            rec.update(_metrics_record(cmTest))
         with open(argv.model + "_metrics.jsonl", "a") as fl:
             fl.write(json.dumps(rec) + "\n")
         print(json.dumps(rec))

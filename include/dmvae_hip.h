@@ -8,6 +8,8 @@
  * loss, autodiff backward, Adam) plus the host batch assembly that feeds it.
  * The reference has no FFI of its own (pure Python over TensorFlow 1.x), so
  * each entry point names the TensorFlow op / reference line it replaces.
+ * Behind the step: evaluation on the device -- clustering accuracy, log-likelihood, t-SNE, and the label-free
+ * and contingency cluster metrics' device half (dmvae_argmax_labels, dmvae_silhouette).
  *
  * Conventions
  *   - plain C: device pointers + sizes, no C++ / torch types.
@@ -641,6 +643,31 @@ int dmvae_tsne_step(void* stream, const dmvae_tsne_config* cfg, void* ws, int64_
 int dmvae_tsne_fit(void* stream, const dmvae_tsne_config* cfg, const float* X, int64_t ldx, const float* Y0, void* ws, int64_t ws_bytes, float* Y,
                    double* kl);
 const float* dmvae_tsne_p(const void* ws);
+
+/* ---- cluster quality on the device (csrc/cluster_metrics.hip): the label of every row, and the silhouette coefficient of rows under
+ * labels (Rousseeuw 1987; sklearn.metrics.silhouette_samples with the Euclidean metric).  The reference reports accuracy alone. ------
+ * dmvae_argmax_labels: labels[r] (device int32 [n_valid]) = the first index of the largest of row r's K scores, scores [n_valid][ld]
+ *   f32 -- np.argmax's rule, exact ties included, the rule of dmvae_confusion_add (the scores hold no NaN; what lies between the rows
+ *   is not read).  1 <= K <= 4096, ld >= K, n_valid >= 0 (DMVAE_EINVAL).
+ * dmvae_silhouette: Z [n][ldz] f32, D columns used (what lies between the rows is not read), labels device int32 [n] in [0, K):
+ *   n_k  = rows with label k
+ *   d_ij = sqrt(sum_c (z_ic - z_jc)^2)              f32 differences summed over c ascending (no norm expansion), correctly rounded sqrt
+ *   a_i  = sum_{j: l_j = l_i} d_ij / (n_{l_i} - 1)
+ *   b_i  = min over k != l_i with n_k > 0 of sum_{j: l_j = k} d_ij / n_k                      (empty clusters are skipped)
+ *   s_i  = (b_i - a_i) / max(a_i, b_i);  0 when n_{l_i} = 1, when max(a_i, b_i) = 0, or when no other cluster has a row
+ *   The rows of a cluster are summed in ascending row order; a running f32 sum takes at most 64 distances before it is added into a
+ *   double; a, b and s are formed in double.  samples (device f32 [n]) receives s_i rounded to f32; out (device double
+ *   [2], 8-byte aligned) receives out[0] = sum_i s_i, added in a fixed order, and out[1] = the number of non-empty clusters.  A label
+ *   outside [0, K) sets bit 0 of *err_flag (device int32, OR-ed into: the caller zeroes it), and that row is left out of every sum and
+ *   gets s = 0.  No float atomics, fixed-order sums: two calls on the same inputs return the same bits.  No N x N or N x K array is
+ *   stored: ws is the caller's scratch of dmvae_silhouette_ws_bytes(n, K) bytes (host arithmetic, linear in n + K), 8-byte aligned.
+ *   The call enqueues only (one memset and five launches) and never synchronises; every index into the rows is 64-bit.  Every argument
+ *   is checked before anything is enqueued; DMVAE_EINVAL: n outside 2 .. 2^20, K outside 1 .. 4096, D < 1, ldz < D, a workspace too
+ *   small or misaligned, a null Z / labels / samples / out / err_flag. */
+int dmvae_argmax_labels(void* stream, const float* scores, int64_t ld, int n_valid, int K, int32_t* labels);
+int64_t dmvae_silhouette_ws_bytes(int64_t n, int K);      /* < 0: an error code */
+int dmvae_silhouette(void* stream, const float* Z, int64_t ldz, int n, int D, const int32_t* labels, int K, void* ws, int64_t ws_bytes,
+                     float* samples, double* out, int32_t* err_flag);
 
 /* Measurement and tuning entry points (per-kernel timing for bench.py's roofline leg, probes, tile knobs) are
  * declared in dmvae_hip_debug.h: exported by the same library, not part of the drop-in boundary. */
