@@ -341,6 +341,16 @@ class DeepMixtureVAE(VAE):
                                      "prior_log_vars": np.log(gmm_model.covariances_ + 1e-20)})
         return gmm_model
 
+    def _fit_prior_host(self, X, n_epochs, n_init):
+        """gmm="host": the same mixture by sklearn on the encoder means (base_models.py:367-390 with n_init = 20, :614-646 with 5)"""
+        from sklearn.mixture import GaussianMixture
+        gmm_model = GaussianMixture(n_components=self.n_classes, covariance_type="diag", max_iter=n_epochs,
+                                    n_init=n_init, weights_init=np.ones(self.n_classes) / self.n_classes)
+        gmm_model.fit(self.encode(X)[0])
+        self._engine.set_parameters({"prior_means": gmm_model.means_,
+                                     "prior_log_vars": np.log(gmm_model.covariances_ + 1e-20)})
+        return gmm_model
+
     def decode(self, Z):
         """reconstructed_X for given Z (what visualization.py:83-87 fetches by feeding model.Z)."""
         import torch
@@ -360,23 +370,33 @@ class DeepMixtureVAE(VAE):
         Z = mean if epsilon is None else mean + np.exp(log_var / 2) * np.asarray(epsilon)
         return self.decode(Z)
 
+    def _eval_order_on_device(self, data, order):
+        """the evaluators' upload: the rows `order` of `data` as the int32 permutation _eval_perm on the device, beside the resident rows"""
+        import torch
+        dev = self._session.device
+        t = torch.as_tensor(np.ascontiguousarray(order, dtype=np.int32))
+        if self._eval_perm is None or self._eval_perm.numel() != t.numel():      # (a buffer of its own: the captured step holds _perm)
+            self._eval_perm = torch.empty(t.numel(), dtype=torch.int32, device=dev)
+        self._eval_perm.copy_(t)
+        return data.device_rows(dev)
+
+    def _eval_batches(self, data, order):
+        """(s, n) of every batch of the rows `order` of `data`, each assembled by load_batch when it is yielded; only enqueues"""
+        rows, eng, N = self._eval_order_on_device(data, order), self._engine, len(order)
+        for s in range(0, N, eng.max_batch):
+            n = min(eng.max_batch, N - s)
+            eng.load_batch(rows, self._eval_perm, s, n)
+            yield s, n
+
     def _device_confusion(self, data, order, R, draws=1, eps=None, counter=0):
         """eval="device": the [R, R] confusion matrix [cluster][class] of the rows `order` of `data`, built on the GPU
         (StepEngine.eval_clusters) from the resident rows and classes.  The loop only enqueues -- batch gather, encoder, arg-max
         and count per batch; the matrix and its error flag come back in ONE copy at the end.  eps: VaDE's host noise, flat on
         the device, batch after batch as [draws, n, latent_dim]."""
-        import torch
-        eng, dev = self._engine, self._session.device
-        rows, cls = data.device_rows(dev), data.device_classes(dev)
-        t = torch.as_tensor(np.ascontiguousarray(order, dtype=np.int32))
-        if self._eval_perm is None or self._eval_perm.numel() != t.numel():      # (a buffer of its own: the captured step holds _perm)
-            self._eval_perm = torch.empty(t.numel(), dtype=torch.int32, device=dev)
-        self._eval_perm.copy_(t)
+        eng, dev, D = self._engine, self._session.device, self.latent_dim
+        cls = data.device_classes(dev)
         conf = eng.confusion_buffer(R, dev)
-        b, N, D = eng.max_batch, len(order), self.latent_dim
-        for s in range(0, N, b):
-            n = min(b, N - s)
-            eng.load_batch(rows, self._eval_perm, s, n)
+        for s, n in self._eval_batches(data, order):
             e = None if eps is None else eps[draws * D * s: draws * D * (s + n)].view(draws, n, D)
             eng.eval_clusters(conf, cls, self._eval_perm, s, n, draws=draws, eps=e, counter=counter)
         return eng.read_confusion(conf)
@@ -399,19 +419,9 @@ class DeepMixtureVAE(VAE):
         get_accuracy(eval="device") does, WITHOUT reshuffling: nothing is drawn from the NumPy stream.  The noise is the device's
         Philox stream 4 keyed by (seed, counter, draw, position of the row): two calls with one counter return the same bits.
         The loop only enqueues; one float64 pair comes back at the end."""
-        import torch
-        eng, dev = self._engine, self._session.device
-        rows = data.device_rows(dev)
-        order = data.order
-        t = torch.as_tensor(np.ascontiguousarray(order, dtype=np.int32))
-        if self._eval_perm is None or self._eval_perm.numel() != t.numel():
-            self._eval_perm = torch.empty(t.numel(), dtype=torch.int32, device=dev)
-        self._eval_perm.copy_(t)
+        eng, N = self._engine, len(data.order)
         acc = eng.loglik_buffer()
-        b, N = eng.max_batch, len(order)
-        for s in range(0, N, b):
-            n = min(b, N - s)
-            eng.load_batch(rows, self._eval_perm, s, n)
+        for s, n in self._eval_batches(data, data.order):
             eng.eval_loglik(acc, n, N, s, k, counter=counter)
         return eng.read_loglik(acc)[0]
 
@@ -432,20 +442,13 @@ class DeepMixtureVAE(VAE):
         import torch
         from dmvae_hip import metrics
         eng, dev = self._engine, self._session.device
-        rows, cls = data.device_rows(dev), data.device_classes(dev)
-        order = data.order
-        t = torch.as_tensor(np.ascontiguousarray(order, dtype=np.int32))
-        if self._eval_perm is None or self._eval_perm.numel() != t.numel():
-            self._eval_perm = torch.empty(t.numel(), dtype=torch.int32, device=dev)
-        self._eval_perm.copy_(t)
+        cls = data.device_classes(dev)
         conf = eng.confusion_buffer(R, dev)
-        b, N, D = eng.max_batch, len(order), self.latent_dim
+        N, D = len(data.order), self.latent_dim
         silhouette = bool(silhouette) and N >= 2
         labels = torch.empty(N, dtype=torch.int32, device=dev)
         Z = torch.empty((N, D), dtype=torch.float32, device=dev) if silhouette else None
-        for s in range(0, N, b):
-            n = min(b, N - s)
-            eng.load_batch(rows, self._eval_perm, s, n)
+        for s, n in self._eval_batches(data, data.order):
             eng.eval_clusters(conf, cls, self._eval_perm, s, n, draws=self._metrics_draws, eps=None, counter=counter)
             eng.eval_labels(labels[s:s + n], n)
             if silhouette:
@@ -596,13 +599,7 @@ class DeepMixtureVAE(VAE):
                 self._fit_prior_on_device(data.data, n_epochs, n_init=20)
                 self._save("prior")
             elif n_epochs > 0:
-                from sklearn.mixture import GaussianMixture
-                Z = self.encode(data.data)[0]
-                gmm_model = GaussianMixture(n_components=self.n_classes, covariance_type="diag", max_iter=n_epochs,
-                                            n_init=20, weights_init=np.ones(self.n_classes) / self.n_classes)
-                gmm_model.fit(Z)
-                self._engine.set_parameters({"prior_means": gmm_model.means_,
-                                             "prior_log_vars": np.log(gmm_model.covariances_ + 1e-20)})
+                self._fit_prior_host(data.data, n_epochs, n_init=20)
                 self._save("prior")
         self._engine.reset_optimizer(self._prior_lr)
         min_loss = float("inf")
@@ -717,13 +714,7 @@ class VaDE(DeepMixtureVAE):
                 self._fit_prior_on_device(data.data, n_epochs, n_init=5)
                 self._save("prior")
             elif n_epochs > 0:
-                from sklearn.mixture import GaussianMixture
-                Z = self.encode(data.data)[0]
-                gmm_model = GaussianMixture(n_components=self.n_classes, covariance_type="diag", max_iter=n_epochs,
-                                            n_init=5, weights_init=np.ones(self.n_classes) / self.n_classes)
-                gmm_model.fit(Z)
-                self._engine.set_parameters({"prior_means": gmm_model.means_,
-                                             "prior_log_vars": np.log(gmm_model.covariances_ + 1e-20)})
+                self._fit_prior_host(data.data, n_epochs, n_init=5)
                 self._save("prior")
 
     def pretrain(self, session, data, n_epochs_vae, n_epochs_prior):

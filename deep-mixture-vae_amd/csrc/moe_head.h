@@ -1,4 +1,4 @@
-// Arguments of the mixture-of-experts row stage (moe_head.hip), shared by the kernel and the step plan (api.hip).
+// Arguments of the mixture-of-experts row stage (moe_head.hip), shared by the kernel and the step plan (step.hip: moe_stage).
 #pragma once
 #include "common.h"
 

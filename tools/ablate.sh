@@ -5,17 +5,22 @@
 set -e
 cd "$(dirname "$0")/../deep-mixture-vae_amd"
 python3 build.py > /dev/null
+# the sources that read measure.h (the host side: step.hip the step without its gather, api.hip the stamp tables)
+ABL="gemm_bf16 latent gemm_bf16_256 heads_dx heads_latent step api"
 for n in "$@"; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -mllvm -amdgpu-mfma-vgpr-form=1 -I ../include -DDMVAE_ABLATE=$n -c csrc/gemm_bf16.hip -o build/gemm_bf16_abl$n.o &
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -I ../include -DDMVAE_ABLATE=$n -c csrc/latent.hip -o build/latent_abl$n.o &
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -mllvm -amdgpu-mfma-vgpr-form=1 -I ../include -DDMVAE_ABLATE=$n -c csrc/gemm_bf16_256.hip -o build/gemm_bf16_256_abl$n.o &
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -mllvm -amdgpu-mfma-vgpr-form=1 -I ../include -DDMVAE_ABLATE=$n -c csrc/heads_dx.hip -o build/heads_dx_abl$n.o &
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -mllvm -amdgpu-mfma-vgpr-form=1 -I ../include -DDMVAE_ABLATE=$n -c csrc/heads_latent.hip -o build/heads_latent_abl$n.o &
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -mllvm -amdgpu-mfma-vgpr-form=1 -I ../include -DDMVAE_ABLATE=$n -c csrc/api.hip -o build/api_abl$n.o &
+  for b in $ABL; do
+    VF="-mllvm -amdgpu-mfma-vgpr-form=1"; if [ $b = latent ]; then VF=""; fi
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 $VF -I ../include -DDMVAE_ABLATE=$n -c csrc/$b.hip -o build/${b}_abl$n.o &
+  done
 done
 wait
 for n in "$@"; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/libdmvae_hip_abl$n.so build/gemm_bf16_abl$n.o build/latent_abl$n.o \
-      build/gemm_bf16_256_abl$n.o build/gemm_f32.o build/latent_mfma.o build/latent_vade.o build/latent_vade_mfma.o build/elementwise.o build/conv.o build/heads_dx_abl$n.o build/heads_latent_abl$n.o build/strip_fwd2.o build/api_abl$n.o
+  objs=""
+  for b in $(python3 -c "import build; print(' '.join(s[:-4] for s in build.SOURCES))"); do
+    use=build/$b.o
+    for a in $ABL; do if [ $a = $b ]; then use=build/${b}_abl$n.o; fi; done
+    objs="$objs $use"
+  done
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/libdmvae_hip_abl$n.so $objs
   echo build/libdmvae_hip_abl$n.so
 done
