@@ -372,6 +372,9 @@ extern "C" int dmvae_plan_view(const dmvae_plan* p, const char* name, void** ptr
     else if (n == "moe_P" && p->moe.on) v = &p->moe.P;      // expert outputs (after a training pass: dP, f32)
     else if (n == "moe_pred" && p->moe.on) v = &p->moe.pred;
     else if (n == "moe_acc" && p->moe.on) v = &p->moe.acc;
+    else if (n == "moe_dP" && p->moe.on) v = &p->moe.dP;    // the expert layer's weight-gradient operand (act dtype)
+    else if (n == "dlogits") v = &a.dlg;                    // act dtype
+    else if (n == "gmu") v = &a.gmu;
     else if (n == "hzc" && !p->vade) v = &a.hzc;   // [z-hidden | c-hidden], halves Hp apart
     else if (n.rfind("enc", 0) == 0 && n.size() == 4 && n[3] - '0' < (int)p->enc.size()) v = &a.enc[n[3] - '0'];
     else if (n.rfind("dec", 0) == 0 && n.size() == 4 && n[3] - '0' < (int)p->dec.size()) v = &a.dec[n[3] - '0'];

@@ -369,6 +369,10 @@ class StepEngine:
         assert perm is None or (perm.dtype == torch.int32 and perm.is_contiguous())
         n_valid = self.max_batch if n_valid is None else int(n_valid)
         self._pf_primed = False
+        if self.moe is not None:
+            # the MoE stage of the passes that follow reads its labels through `perm` (step.hip: batch_rows keeps the pointer): a temporary
+            # would go back to the allocator here and be handed to the caller's next tensor (eps, gumbel) before the pass has run
+            self._batch_src = (data, perm)
         check(lib.dmvae_plan_load_batch(self._plan, self._stream(), ptr(data), data.shape[0], ptr(perm),
                                         int(first), n_valid, 1 if use_state_cursor else 0), "dmvae_plan_load_batch")
 
@@ -677,7 +681,8 @@ class StepEngine:
 
     def view(self, name, rows=None, cols=None):
         """torch view of a workspace tensor ("mean", "log_var", "logits", "weights",
-        "recon", "x", "Z", "dxlogits"; VaDE: "eval_w", what eval_clusters averaged)."""
+        "recon", "x", "Z", "dxlogits"; VaDE: "eval_w", what eval_clusters averaged; for the tests: "dlogits" (act dtype), "gmu",
+        and with a MoE attachment "moe_P", "moe_pred", "moe_dP" (act dtype))."""
         p, ld, dt = C.c_void_p(), C.c_int64(), C.c_int32()
         check(lib.dmvae_plan_view(self._plan, name.encode(), C.byref(p), C.byref(ld), C.byref(dt)), "dmvae_plan_view")
         tdt = torch.bfloat16 if dt.value == _lib.BF16 else torch.float32
@@ -696,6 +701,8 @@ class StepEngine:
                      "weights": self.n_classes, "eval_w": self.n_classes, "recon": self.input_dim, "x": self.input_dim,
                      "moe_pred": self.moe["output_dim"] if self.moe else 0,
                      "moe_P": self.moe["n_experts"] * self.moe["output_dim"] if self.moe else 0,
+                     "moe_dP": self.moe["n_experts"] * self.moe["output_dim"] if self.moe else 0,
+                     "dlogits": self.n_classes, "gmu": self.latent_dim,
                      "Z": self.latent_dim, "dxlogits": self.input_dim}.get(name, ld.value)
         return t[: (self.max_batch if rows is None else rows), : (full_cols if cols is None else cols)]
 

@@ -122,3 +122,78 @@ def backward(p, cfg, a, E, Od, featLearn, classification, lossVAE):
 def classification_labels(classes, n_classes):
     """one-hot over the dataset's classes"""
     return np.eye(n_classes)[np.asarray(classes, dtype=np.int64)]
+
+
+def dlogits_from(q, dq):
+    """softmax backward of the gate, float64: dlogits = q (dq - sum_e q dq)"""
+    q, dq = np.asarray(q, np.float64), np.asarray(dq, np.float64)
+    return q * (dq - np.sum(q * dq, axis=1, keepdims=True))
+
+
+# ---- the float32 yardstick: csrc/moe_head.hip restated in NumPy float32, in the kernel's order of operations
+def head_f32(P, logits, Y, classification, inv_B, mean=None, W=None, bias=None):
+    """moe_head_kernel's own algebra in float32: max-subtracted gate softmax and expert softmaxes, u, U, p, gp, gpp, g, per-expert dq and dP,
+    qdq, dlogits; with mean / W / bias (featLearn) P = relu(mean) . W + bias accumulated over d, and gmu.  Every sum (over e, o, d, the batch) is a
+    SEQUENTIAL float32 accumulation: the kernel's lane-blocked and shuffled orders should do no worse.  exp and log as the kernel takes them
+    (__expf(x) = exp2(fl(x log2 e)), __logf(x) = fl(log2 x) ln 2; helpers/trained_latents.py: _Arith).  Shares nothing with head_forward /
+    head_backward but the inputs.  P [B, E, O] (None with featLearn: the head then runs on P_fl, its own product), logits [B, E], Y [B, O], W [D, E*O], bias [E*O], mean [B, D].
+    Returns float64 copies of the float32 results: P, P_fl (featLearn), q, pred, dP, dq, dlogits, loss_rows, err_rows, loss, err (the batch scalars of
+    moe_finalize_kernel: inv_B sum loss_rows; classification: sum err_rows, regression: inv_B sum err_rows) and, featLearn, gmu."""
+    from trained_latents import _Arith
+    f32 = np.float32
+    A = _Arith(f32)
+    lg, Y = np.asarray(logits).astype(f32), np.asarray(Y).astype(f32)
+    B, E = lg.shape
+    Od = Y.shape[1]
+    inv_B = f32(inv_B)
+    if mean is not None:
+        mean, W, bias = np.asarray(mean).astype(f32), np.asarray(W).astype(f32), np.asarray(bias).astype(f32)
+        x = np.maximum(mean, f32(0))
+        P_fl = A.seq(mean.shape[1] + 1, lambda d: np.broadcast_to(bias[None], (B, E * Od)).astype(f32) if d == 0 else x[:, d - 1, None] * W[None, d - 1])
+        P_fl = P_fl.reshape(B, E, Od)
+    P = P_fl if P is None else np.asarray(P).astype(f32).reshape(B, E, Od)
+    ge = A.exp(lg - lg.max(1, keepdims=True))
+    ginv = f32(1) / A.seq(E, lambda e: ge[:, e])
+    q = ge * ginv[:, None]
+    out = dict(P=P, q=q)
+    if mean is not None:
+        out["P_fl"] = P_fl
+    if classification:
+        ex = A.exp(P - P.max(2, keepdims=True))
+        s = ex * (f32(1) / A.seq(Od, lambda o: ex[:, :, o]))[:, :, None]
+        u = A.seq(E, lambda e: q[:, e, None] * s[:, e])
+        iU = f32(1) / A.seq(Od, lambda o: u[:, o])
+        pr = u * iU[:, None]
+        lp = A.log(pr + f32(1e-20))
+        loss_rows = f32(1000) * A.seq(Od, lambda o: -(Y[:, o] * lp[:, o]))
+        top = np.argmax(pr, axis=1)                                      # first index on ties
+        hot = (np.arange(Od)[None] == top[:, None]).astype(f32)
+        err_rows = f32(0.5) * A.seq(Od, lambda o: np.abs(Y[:, o] - hot[:, o]))
+        gp = (f32(-1000) * inv_B) * Y / (pr + f32(1e-20))
+        gpp = A.seq(Od, lambda o: gp[:, o] * pr[:, o])
+        g = (gp - gpp[:, None]) * iU[:, None]
+        sg = A.seq(Od, lambda o: s[:, :, o] * g[:, None, o])            # [B, E]: sum_o s g, which is dq as well
+        dq = sg
+        dP = (q[:, :, None] * s) * (g[:, None, :] - sg[:, :, None])
+        pred = pr
+    else:
+        u = A.seq(E, lambda e: q[:, e, None] * P[:, e])
+        r = u - Y
+        l = A.seq(Od, lambda o: r[:, o] * r[:, o])
+        loss_rows, err_rows = f32(0.5) * l, l
+        g = inv_B * r
+        dq = A.seq(Od, lambda o: P[:, :, o] * g[:, None, o])
+        dP = q[:, :, None] * g[:, None, :]
+        pred = u
+    qdq = A.seq(E, lambda e: q[:, e] * dq[:, e])
+    dl = q * (dq - qdq[:, None])
+    loss = A.seq_rows(loss_rows) * inv_B
+    err = A.seq_rows(err_rows) * (f32(1) if classification else inv_B)
+    out.update(pred=pred, dP=dP, dq=dq, dlogits=dl, loss_rows=loss_rows, err_rows=err_rows, loss=loss, err=err)
+    if mean is not None:
+        dPf = dP.reshape(B, E * Od)
+        acc = A.seq(E * Od, lambda c: dPf[:, c, None] * W[None, :, c])
+        out["gmu"] = np.where(mean > 0, acc, f32(0))
+    for k, v in out.items():
+        assert np.asarray(v).dtype == f32, (k, np.asarray(v).dtype)
+    return {k: (float(v) if np.ndim(v) == 0 else np.asarray(v, np.float64)) for k, v in out.items()}

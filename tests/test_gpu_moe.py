@@ -63,8 +63,21 @@ def run_step(eng, X, Y, rng, n, latent, E, mode):
 @pytest.mark.parametrize("featLearn", [0, 1])
 @pytest.mark.parametrize("mode", ["exact", "relaxed"])
 def test_fp32_step_against_the_oracle(model, classification, featLearn, mode):
-    E, Od, n = 5, 7, 93                      # ragged: 93 real rows of a 128-row plan
-    latent = 1 if model == "dmoe" else 8     # DeepMoE gates with a latent_dim = 1 DMVAE (models.py:240-243)
+    step_against_the_oracle(model, classification, featLearn, mode)
+
+
+# the widths at which moe_head_kernel takes another path (tests/helpers/moe_cases.py): one output in the second slot of a lane with E no multiple
+# of 16 and D > 32; all four slots full; sixteen experts per lane.  dvmoe, both modes; not the full cross product
+@pytest.mark.parametrize("classification,featLearn", [(1, 1), (0, 0)])
+@pytest.mark.parametrize("mode", ["exact", "relaxed"])
+@pytest.mark.parametrize("shape", [(40, 17, 33), (16, 64, 24), (256, 4, 4)], ids=lambda s: "%dx%dx%d" % s)
+def test_fp32_step_against_the_oracle_at_shape(shape, mode, classification, featLearn):
+    step_against_the_oracle("dvmoe", classification, featLearn, mode, shape)
+
+
+def step_against_the_oracle(model, classification, featLearn, mode, shape=(5, 7, 8)):
+    E, Od, n = shape[0], shape[1], 93        # ragged: 93 real rows of a 128-row plan
+    latent = 1 if model == "dmoe" else shape[2]     # DeepMoE gates with a latent_dim = 1 DMVAE (models.py:240-243)
     lossVAE = 1 if model == "dvmoe" else 0
     eng, X, Y, rng = make(E, Od, featLearn, classification, lossVAE, 100, latent=latent, mode=mode)
     p = {k: v.astype(np.float64) for k, v in eng.get_parameters().items()}

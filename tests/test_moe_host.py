@@ -1,6 +1,10 @@
 """Host-side tests of the mixture-of-experts models (no GPU): the float64 restatement against torch autograd, the label
 generators and MEDataset against the reference's semantics (code/includes/utils.py:37-74, 378-425), the CLI dispatch and the
-C ABI of the new entries."""
+C ABI of the new entries; and what tests/test_gpu_moe_head.py rests on (tests/helpers/moe_cases.py, moe_oracle.head_f32): the float64
+backward of the head is the derivative of its forward at every shape of the GPU tests, the float32 yardstick meets on its own the bars
+the kernel is held to, every "trained" classification case is in the regime it is named after, and the arg-max of nearly every row is
+decided by more than the yardstick's error (pytest -s prints, per case, the clear-row share, the smallest true-label probability and
+max |dq|)."""
 import os
 import re
 import sys
@@ -12,6 +16,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hel
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 import dmvae_oracle as O      # noqa: E402
+import moe_cases as MC        # noqa: E402
 import moe_oracle as MO       # noqa: E402
 
 
@@ -262,3 +267,113 @@ def test_attach_limits_on_the_host():
     assert t1["prior_means"][0] == t1["b_moe"][0] + 128
     assert all(t1[k][0] == t0[k][0] for k in t0 if k.startswith("W_"))      # weights keep their offsets
     assert s1.param_elems > s0.param_elems and s1.work_bytes > s0.work_bytes
+
+
+# ---- the cases of tests/test_gpu_moe_head.py
+CASES = [(s, k, c, f) for s in MC.SHAPES for k in MC.KINDS for c in (1, 0) for f in (0, 1)]
+IDS = [MC.case_id(*c) for c in CASES]
+
+
+def run(shape, kind, classification, featLearn):
+    c = MC.get_case(shape, kind, classification, featLearn)
+    h = MC.head_inputs(c)
+    kw = dict(mean=h["mean"], W=c["params"]["W_moe"], bias=c["params"]["b_moe"]) if featLearn else {}
+    o = MC.oracle(h["logits"], h["P"], h["Y"], classification, 1.0 / MC.N, **kw)
+    y = MC.yardstick(h["logits"], h["P"], h["Y"], classification, 1.0 / MC.N, **kw)
+    return c, h, o, y
+
+
+@pytest.mark.parametrize("shape", MC.SHAPES, ids=lambda s: "%dx%dx%d" % s)
+@pytest.mark.parametrize("classification", [1, 0])
+def test_float64_backward_is_the_derivative_of_the_forward(shape, classification):
+    """central differences of inv_B sum_b loss_rows in P and in q (q as a free variable, as head_backward takes it), on the mild case: 24 entries
+    of each, among them the last expert's last output of the last row.  h = 1e-5 on O(1) inputs: truncation ~1e-10, rounding ~1e-16 L / h ~ 1e-7 of
+    a loss of ~1e4 / n -- the bar is 1e-6 of the largest gradient entry plus 1e-7."""
+    c = MC.get_case(shape, "mild", classification, 0)
+    hin = MC.head_inputs(c)
+    P, Y = hin["P"], hin["Y"]
+    q = MC.O.softmax(hin["logits"])
+    inv_B = 1.0 / MC.N
+    f = lambda P_, q_: MO.head_forward(P_, q_, Y, classification)["loss_rows"].sum() * inv_B
+    dP, dq = MO.head_backward(MO.head_forward(P, q, Y, classification), classification, inv_B)
+    rng = np.random.RandomState(7)
+    h = 1e-5
+    for arr, grad, which in ((P, dP, 0), (q, dq, 1)):
+        idx = [tuple(s - 1 for s in arr.shape)] + [tuple(rng.randint(0, s) for s in arr.shape) for _ in range(23)]
+        bar = 1e-6 * np.abs(grad).max() + 1e-7
+        for i in idx:
+            hi, lo = arr.copy(), arr.copy()
+            hi[i] += h
+            lo[i] -= h
+            fd = ((f(hi, q) - f(lo, q)) if which == 0 else (f(P, hi) - f(P, lo))) / (2 * h)
+            assert abs(fd - grad[i]) <= bar, (which, i, fd, grad[i], bar)
+
+
+def test_dlogits_from_is_the_softmax_backward():
+    rng = np.random.RandomState(0)
+    lg, dq = rng.randn(6, 9), rng.randn(6, 9)
+    q = MC.O.softmax(lg)
+    h = 1e-6
+    for i in [(0, 0), (3, 8), (5, 4)]:
+        hi, lo = lg.copy(), lg.copy()
+        hi[i] += h
+        lo[i] -= h
+        fd = (np.sum(MC.O.softmax(hi) * dq) - np.sum(MC.O.softmax(lo) * dq)) / (2 * h)
+        assert abs(fd - MO.dlogits_from(q, dq)[i]) <= 1e-8
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_yardstick_meets_the_bars_on_its_own(case, capsys):
+    """head_f32 against the float64 oracle under the project's bars alone (MC.project_bar: no help from itself), and what the case promises"""
+    shape, kind, classification, featLearn = case
+    c, h, o, y = run(*case)
+    names = ("pred", "dP", "dlogits", "loss", "err") + (("P_fl", "gmu") if featLearn else ())
+    for k in names:
+        rtol, atol = MC.project_bar(k, o[k])
+        atol = max(atol, 2.0 ** -126)       # what float32 cannot hold at all: (2, 1, 5) trained regression has max |dlogits| = 1e-77 in the oracle
+        ok, err, _ = MC.within(k, y[k], o[k], y[k], tol=(rtol, atol))
+        assert ok, (k, err, (rtol, atol))
+    if featLearn:       # the collapsed latent dimension: mean = 0.0 exactly, where [mean > 0] and [mean >= 0] differ
+        assert not np.any(h["mean"][:, -1]) and np.any(c["params"]["W_moe"][-1]) and not np.any(o["gmu"][:, -1])
+    line = MC.case_id(*case)
+    if classification:
+        clear = MC.clear_rows(o["pred"], y["pred"])
+        p_true = np.sum(o["pred"] * h["Y"], axis=1)
+        line += ": clear rows %.3f, min true-label p %.2e, max |dq| %.2e, gate weights 0.0f %d" % (
+            clear.mean(), p_true.min(), np.abs(o["dq"]).max(), int((y["q"] == 0).sum()))
+        assert clear.mean() >= 0.95
+        # the yardstick's error count is the oracle's on the clear rows
+        assert np.array_equal(y["err_rows"][clear], o["err_rows"][clear])
+        if kind == "trained" and shape[1] > 1:          # (O = 1: p = 1 in every row, the loss and every gradient are 0: no regime to be in)
+            assert p_true.min() < 1e-30
+            assert np.any(y["q"] == 0.0)
+            assert np.abs(o["dq"]).max() > 1e15
+            wrong = o["err_rows"].sum() / MC.N
+            assert 0.05 <= wrong <= 0.2, wrong
+        if shape[1] == 1:
+            assert o["loss"] == 0.0 and not np.any(o["dP"]) and not np.any(o["dlogits"])
+    else:
+        line += ": max |pred| %.2e" % np.abs(o["pred"]).max()
+    with capsys.disabled():
+        print("\n  " + line, end="")
+
+
+def test_trained_gate_is_one_hot_and_dead_experts_are_zero_in_float32():
+    for shape in MC.SHAPES:
+        c, h, o, y = run(shape, "trained", 1, 0)
+        E = shape[0]
+        dead = np.arange(E) >= E - MC.n_dead(E)
+        assert not np.any(y["q"][:, dead]) and np.all(o["q"][:, dead] > 0)          # 0.0 in float32, not in the oracle
+        if E - MC.n_dead(E) > 1:
+            assert np.median(o["q"].max(1)) > 0.99
+
+
+def test_the_yardstick_sees_a_wrong_kernel():
+    """the bars are not vacuous: the algebra with one mistake in it (no `- qdq`; the last output slot dropped from dP) misses them by far"""
+    c, h, o, y = run((16, 64, 24), "mild", 0, 0)          # regression: in classification sum_e q dq = sum_o p gp - gpp is analytically 0
+    bad = y["q"] * y["dq"]
+    assert not MC.within("dlogits", bad, o["dlogits"], y["dlogits"])[0]
+    c, h, o, y = run((16, 64, 24), "mild", 1, 0)
+    dP = y["dP"].copy()
+    dP[:, :, 48:] = 0
+    assert not MC.within("dP", dP, o["dP"], y["dP"])[0]
