@@ -467,6 +467,36 @@ class DeepMixtureVAE(VAE):
                 res["silhouette"] = total / N
         return (res, labels.cpu().numpy()) if return_labels else res
 
+    def get_posterior_diagnostics(self, session, data, counter=0, max_points=None, au_threshold=0.01, eps=None, return_points=False):
+        """What the KL term bought: dict(mi, marginal_kl, rate, mi_cap, active_units, var_of_mean, mean_of_var, n_points, n_rows) of
+        `data` (dmvae_hip.density, csrc/mixture_density.hip).  With z_i ~ q(z|x_i) one sample per point, a_i = log q(z_i|x_i),
+        m_i = log q(z_i) under the aggregate posterior 1/N sum_n q(z|x_n) over ALL n_rows rows (the row itself included) and p_i = log p(z_i)
+        under the marginal mixture prior: mi = mean(a - m), the estimate of I(x;z) of He et al. 2019, at most mi_cap = log n_rows;
+        marginal_kl = mean(m - p), the mismatch KL(q(z) || p(z)); rate = mean(a - p), their sum (Hoffman & Johnson 2016).
+        var_of_mean[d] / mean_of_var[d]: the population variance of the encoder means / the mean encoder variance of dimension d;
+        active_units = #{d: var_of_mean[d] > au_threshold} (Burda et al. 2016).  max_points = M < n_rows scores the rows floor(i n_rows / M)
+        only (still against all rows).  Walks the data set in its current order WITHOUT reshuffling, draws nothing from NumPy and writes
+        no parameter, moment or step state: the noise is eps ([n_points][latent_dim], NumPy or device) or the device's Philox stream 6
+        keyed by (seed, counter).  The loop only enqueues -- gather, encoder, device copies of the mean and log_var views -- then the
+        sample, two all-pairs log-density calls, the column statistics and three float64 sums; one small copy comes back at the end.
+        return_points: (the dict, z [n_points][latent_dim], a [n_points]) with the device tensors of the sample instead."""
+        import torch
+        from dmvae_hip import density
+        eng, dev = self._engine, self._session.device
+        N, D = len(data.order), self.latent_dim
+        mean = torch.empty((N, D), dtype=torch.float32, device=dev)
+        log_var = torch.empty((N, D), dtype=torch.float32, device=dev)
+        for s, n in self._eval_batches(data, data.order):
+            eng.encode(n)
+            mean[s:s + n].copy_(eng.view("mean", n))
+            log_var[s:s + n].copy_(eng.view("log_var", n))
+        if eps is not None and not isinstance(eps, torch.Tensor):
+            eps = torch.as_tensor(np.ascontiguousarray(np.asarray(eps, dtype=np.float32))).to(dev)
+        enq = density.posterior_diagnostics_enqueue(mean, log_var, eng.param_view("prior_means"), eng.param_view("prior_log_vars"), seed=self.seed,
+                                                    counter=counter, max_points=max_points, eps=eps)
+        res = density.diagnostics_from(enq, au_threshold)
+        return (res, enq["z"], enq["a"]) if return_points else res
+
     # ------------------------------------------------------------------ pretraining (base_models.py:304-423)
     # the variables tf.get_collection(TRAINABLE_VARIABLES, scope=name + "/encoder_network/c") returns (:313-315)
     PRIOR_VAR_LIST = ("W_ch", "b_ch", "W_logits", "b_logits")

@@ -17,6 +17,7 @@
 #include "eval_loglik.h"
 #include "tsne.h"
 #include "cluster_metrics.h"
+#include "mixture_density.h"
 #include "measure.h"
 
 namespace dmvae {
@@ -235,6 +236,22 @@ extern "C" int dmvae_silhouette(void* stream, const float* Z, int64_t ldz, int n
                                 float* samples, double* out, int32_t* err_flag) {
     return silhouette_launch((hipStream_t)stream, Z, ldz, n, D, labels, K, ws, ws_bytes, samples, out, err_flag);
 }
+extern "C" int64_t dmvae_mixture_logpdf_ws_bytes(int64_t M, int64_t J, int64_t D) { return mixture_logpdf_ws_bytes(M, J, D); }
+extern "C" int dmvae_mixture_logpdf(void* stream, const float* Z, int64_t ldz, int M, int D, const float* mean, int64_t ldm, const float* log_var, int64_t ldv,
+                                    int J, const float* log_w, void* ws, int64_t ws_bytes, float* out) {
+    return mixture_logpdf_launch((hipStream_t)stream, Z, ldz, M, D, mean, ldm, log_var, ldv, J, log_w, ws, ws_bytes, out);
+}
+extern "C" int dmvae_mixture_logpdf_split(int M, int J, int D) { return mixture_logpdf_split(M, J, D).nsplit; }
+extern "C" int dmvae_posterior_sample(void* stream, const float* mean, int64_t ldm, const float* log_var, int64_t ldv, int n, int D, const float* eps,
+                                      int64_t ld_eps, uint64_t seed, uint64_t counter, int64_t pos0, float* Z, int64_t ldz, float* logq) {
+    return posterior_sample_launch((hipStream_t)stream, mean, ldm, log_var, ldv, n, D, eps, ld_eps, seed, counter, pos0, Z, ldz, logq);
+}
+extern "C" int64_t dmvae_column_stats_ws_bytes(int64_t n, int64_t D) { return column_stats_ws_bytes(n, D); }
+extern "C" int dmvae_column_stats(void* stream, const float* mean, int64_t ldm, const float* log_var, int64_t ldv, int n, int D, void* ws, int64_t ws_bytes,
+                                  double* out) {
+    return column_stats_launch((hipStream_t)stream, mean, ldm, log_var, ldv, n, D, ws, ws_bytes, out);
+}
+extern "C" int dmvae_sum_f64(void* stream, const float* x, int64_t n, double* out) { return sum_f64_launch((hipStream_t)stream, x, n, out); }
 extern "C" int dmvae_recon_nblocks(int B_pad, int I_pad) { return recon_nblocks(B_pad, I_pad); }
 extern "C" int dmvae_recon_fwd_bwd(void* stream, int act_dtype, int recon_kind, int B, int B_pad, int I, int I_pad, const float* logits,
                                    int64_t ldl, const float* x, int64_t ldx, float inv_B, void* dl, int64_t ldd, float* partials) {

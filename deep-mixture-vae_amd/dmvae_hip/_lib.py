@@ -44,6 +44,8 @@ EXPORTS = [
     "dmvae_plan_eval_loglik_ws_bytes", "dmvae_plan_eval_loglik",
     "dmvae_tsne_ws_bytes", "dmvae_tsne_joint_p", "dmvae_tsne_gradient", "dmvae_tsne_step", "dmvae_tsne_fit", "dmvae_tsne_p",
     "dmvae_argmax_labels", "dmvae_silhouette_ws_bytes", "dmvae_silhouette",
+    "dmvae_mixture_logpdf_ws_bytes", "dmvae_mixture_logpdf_split", "dmvae_mixture_logpdf", "dmvae_posterior_sample", "dmvae_column_stats_ws_bytes",
+    "dmvae_column_stats", "dmvae_sum_f64",
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
     "dmvae_debug_conv_first_fwd", "dmvae_debug_conv_first_dw", "dmvae_debug_zero_border", "dmvae_debug_maxpool2_fwd", "dmvae_debug_maxpool2_bwd_relu",
     "dmvae_debug_conv_wflip", "dmvae_debug_conv_gemm", "dmvae_debug_conv_dw",
@@ -256,6 +258,13 @@ def _load():
         "dmvae_argmax_labels": [vp, vp, i64, i32, i32, vp],
         "dmvae_silhouette_ws_bytes": [i64, i32],
         "dmvae_silhouette": [vp, vp, i64, i32, i32, vp, i32, vp, i64, vp, vp, vp],
+        "dmvae_mixture_logpdf_ws_bytes": [i64, i64, i64],
+        "dmvae_mixture_logpdf_split": [i32, i32, i32],
+        "dmvae_mixture_logpdf": [vp, vp, i64, i32, i32, vp, i64, vp, i64, i32, vp, vp, i64, vp],
+        "dmvae_posterior_sample": [vp, vp, i64, vp, i64, i32, i32, vp, i64, u64, u64, i64, vp, i64, vp],
+        "dmvae_column_stats_ws_bytes": [i64, i64],
+        "dmvae_column_stats": [vp, vp, i64, vp, i64, i32, i32, vp, i64, vp],
+        "dmvae_sum_f64": [vp, vp, i64, vp],
         "dmvae_prof_enable": [i32],
         "dmvae_debug_spin": [vp, i32],
         "dmvae_debug_strip_fwd2": [vp, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64],
@@ -290,6 +299,8 @@ def _load():
     lib.dmvae_tsne_ws_bytes.restype = C.c_int64
     lib.dmvae_tsne_p.restype = C.c_void_p
     lib.dmvae_silhouette_ws_bytes.restype = C.c_int64
+    lib.dmvae_mixture_logpdf_ws_bytes.restype = C.c_int64
+    lib.dmvae_column_stats_ws_bytes.restype = C.c_int64
     lib.dmvae_plan_destroy.restype = None
     got = lib.dmvae_abi_version()
     if got != ABI_VERSION:       # the public structs grew between versions: a mismatched pair would read past them

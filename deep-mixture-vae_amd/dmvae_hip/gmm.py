@@ -235,3 +235,23 @@ class DiagGMM:
         if cen is not None:
             self.restarts_["kmeans_iter"] = o["kmeans_iters"]
         return self
+
+    def score_samples_device(self, Z):
+        """log sum_k w_k N(z; mean_k, diag cov_k) of every row of Z as a device f32 [N] (dmvae_mixture_logpdf: any K * D); only enqueues"""
+        from .density import mixture_logpdf
+        if not hasattr(self, "means_"):
+            raise RuntimeError("DiagGMM.score_samples: fit first (or set weights_, means_, covariances_)")
+        with np.errstate(divide="ignore"):
+            lw = np.log(np.asarray(self.weights_, dtype=np.float64))
+        return mixture_logpdf(Z, np.asarray(self.means_, dtype=np.float32), np.log(np.asarray(self.covariances_, dtype=np.float64)).astype(np.float32),
+                              lw.astype(np.float32))
+
+    def score_samples(self, Z):
+        """sklearn's GaussianMixture.score_samples: the weighted log-likelihood of every row of Z, NumPy float64 [N]"""
+        return self.score_samples_device(Z).cpu().numpy().astype(np.float64)
+
+    def score(self, Z):
+        """sklearn's GaussianMixture.score: the mean of score_samples(Z), summed in float64 on the device"""
+        from .density import sum_f64
+        s = self.score_samples_device(Z)
+        return float(sum_f64(s).item()) / s.numel()

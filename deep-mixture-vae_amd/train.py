@@ -16,6 +16,7 @@ New flags (defaults = reference behaviour): --batch_size, --dtype, --seed,
 --eval (host | device: where get_accuracy takes its arg-max and confusion matrix),
 --loglik S (dmvae / vade: held-out log-likelihood of the test set per epoch, the importance-weighted bound with S draws; 0 = off),
 --metrics (per epoch: NMI, ARI, purity and the silhouette coefficient of the test set's latent means beside the accuracy, get_cluster_metrics),
+--diagnostics (dmvae / vade, per epoch on the test set: the estimate of I(x;z), KL(q(z) || p(z)) and the active units, get_posterior_diagnostics),
 --tsne (off | host | device: with --plotting, sampled.png gains the t-SNE scatter of the prior samples, embedded by sklearn on the CPU or by
 the exact t-SNE in HIP, dmvae_hip.tsne.TSNE).
 """
@@ -95,6 +96,10 @@ parser.add_argument("--loglik", type=int, default=0,
 parser.add_argument("--metrics", action="store_true", default=False,
                     help="per epoch, beside the accuracy: NMI, ARI and purity of the test set's clusters against its classes and the silhouette "
                          "coefficient of its latent means, computed on the device (get_cluster_metrics); adds nmiTest / silTest to the epoch line")
+parser.add_argument("--diagnostics", action="store_true", default=False,
+                    help="dmvae / vade, per epoch on the test set: how much of the KL term is information about x (miTest, at most log N), how much "
+                         "is mismatch between the aggregate posterior and the mixture prior, and how many latent dimensions are active (auTest), "
+                         "all pairs on the device (get_posterior_diagnostics); rank 0 alone evaluates")
 parser.add_argument("--tsne", type=str, default="off", choices=["off", "host", "device"],
                     help="--plotting: add the t-SNE scatter of the prior samples (1000 per cluster) to sampled.png, embedded with sklearn on the "
                          "host (the reference's call) or with the exact t-SNE on the device (dmvae_hip.tsne.TSNE); off = the sample grid alone")
@@ -107,6 +112,12 @@ def _metrics_record(cm):
     sil = float(cm["silhouette"])
     return dict(nmi_test=float(cm["nmi"]), ari_test=float(cm["ari"]), purity_test=float(cm["purity"]),
                 silhouette_test=None if math.isnan(sil) else sil, clusters_used_test=int(cm["n_clusters_used"]))
+
+
+def _diagnostics_record(pd):
+    """the JSONL keys of --diagnostics"""
+    return dict(mi_test=float(pd["mi"]), marginal_kl_test=float(pd["marginal_kl"]), rate_test=float(pd["rate"]), mi_cap_test=float(pd["mi_cap"]),
+                active_units_test=int(pd["active_units"]))
 
 
 def main(argv):
@@ -219,6 +230,8 @@ def main(argv):
             eval_seconds = time.perf_counter() - t_eval
             llTest = model.get_log_likelihood(sess, test_data, k=argv.loglik, counter=epoch) if argv.loglik > 0 else None
             cmTest = model.get_cluster_metrics(sess, test_data, counter=epoch) if argv.metrics else None
+            # (rank 0 alone: the call holds no collective and every rank would compute the same figures)
+            pdTest = model.get_posterior_diagnostics(sess, test_data, counter=epoch) if argv.diagnostics and rank == 0 else None
             improved = accTest > maxAcc
             if world > 1:
                 # the branch below holds a COLLECTIVE (sync_master): rank 0 decides and every rank follows.  Each rank scores the same
@@ -249,6 +262,8 @@ def main(argv):
                     rec.update(ll_test=float(llTest), loglik_draws=argv.loglik)
                 if cmTest is not None:
                     rec.update(_metrics_record(cmTest))
+                if pdTest is not None:
+                    rec.update(_diagnostics_record(pdTest))
                 with open(argv.model + "_metrics.jsonl", "a") as fl:
                     fl.write(json.dumps(rec) + "\n")
             if math.isnan(loss):
@@ -259,6 +274,8 @@ def main(argv):
                 postfix["llTest"] = "%.4f" % llTest
             if cmTest is not None:
                 postfix.update(nmiTest="%.4f" % cmTest["nmi"], silTest="%.4f" % cmTest["silhouette"])
+            if pdTest is not None:
+                postfix.update(miTest="%.4f" % pdTest["mi"], auTest="%d" % pdTest["active_units"])
             bar.set_postfix(postfix)
     if plotting:                                                  # train.py:332-334
         visualization.mnist_sample_plot(model, sess, tsne=argv.tsne != "off", tsne_backend=argv.tsne if argv.tsne != "off" else "host")

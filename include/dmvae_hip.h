@@ -669,6 +669,47 @@ int64_t dmvae_silhouette_ws_bytes(int64_t n, int K);      /* < 0: an error code 
 int dmvae_silhouette(void* stream, const float* Z, int64_t ldz, int n, int D, const int32_t* labels, int K, void* ws, int64_t ws_bytes,
                      float* samples, double* out, int32_t* err_flag);
 
+/* ---- posterior diagnostics on the device (csrc/mixture_density.hip): the log-density of points under a diagonal
+ * Gaussian mixture with any number of components, samples of the encoder posteriors, and the column statistics of the encoder outputs.
+ * The reference has none of it.  Definitions, for rows n < N with encoder outputs mu_n and lv_n = log-variance (f32) and points i < M:
+ *   z_i = mu_i + exp(lv_i / 2) eps_i
+ *   a_i = log q(z_i | x_i) = -1/2 sum_d (eps_id^2 + lv_id) - (D/2) log 2 pi
+ *   m_i = log q(z_i)       = logsumexp_j [ -1/2 sum_d ((z_id - mu_jd)^2 exp(-lv_jd) + lv_jd) ] - (D/2) log 2 pi - log N      (all N rows, j = i included)
+ *   p_i = log p(z_i)       = the same over the K prior rows, - log K (the marginal mixture prior)
+ *   mi = mean_i (a_i - m_i) <= mi_cap = log N (He et al. 2019);  marginal_kl = mean_i (m_i - p_i);  rate = mean_i (a_i - p_i) = mi + marginal_kl
+ *   var_of_mean[d] = Var_n mu_nd (population);  mean_of_var[d] = mean_n exp(lv_nd);  active_units = #{d : var_of_mean[d] > threshold}
+ * dmvae_mixture_logpdf: out[i] (device f32 [M]) = logsumexp_{j < J} (log_w[j] + log N(z_i; mu_j, diag exp(lv_j))), the -(D/2) log 2 pi
+ *   included.  Z [M][ldz], mean [J][ldm], log_var [J][ldv] f32, D columns used, read where they are; log_w device f32 [J] or NULL =
+ *   uniform weights, -log J.  An entry of -inf is a component of weight 0: it contributes nothing, also when it is the nearest one; if
+ *   every entry is -inf the result is -inf.  Finite inputs never give NaN.  Arithmetic: exp(-lv) by __expf and c_j = log_w[j] - 1/2 sum_d
+ *   lv_jd (the sum in double) are prepared into the workspace; the quadratic form in the DIFFERENCE form -- e = z - mu, e * e, fma with
+ *   exp(-lv), d ascending in f32 (no norm expansion: it cancels at variances of 1e-6); t_ij = c_j - Q_ij / 2 in f32; the logsumexp as a running
+ *   (max f32, sum f64) with one __expf per pair, the pairs joined in a fixed order; log in double, the constants added in double, one
+ *   rounding to f32.  Per-point error bound, with w_ij the responsibilities and u = 2^-24:
+ *     u [ (D + 5 + max |lv|) sum_j w_ij (Q_ij / 2 + 1/2 sum_d |lv_jd|) + 8 (|out_i| + 1) ]
+ *   Few points against many components: J is split across workgroups into partial (max, sum) pairs in the workspace, joined by a second
+ *   launch; the split is a function of (M, J, D) alone (dmvae_mixture_logpdf_split returns the number of parts: 1 when ceil(M / 16) >= 1024 or
+ *   J <= 256).  Nothing read from ws depends on what it held before the call.  No float atomics: two calls return the same bits.  ws:
+ *   dmvae_mixture_logpdf_ws_bytes(M, J, D) bytes (host arithmetic), 8-byte aligned.  Three or four launches, no synchronisation.  Every
+ *   argument is checked before anything is enqueued; DMVAE_EINVAL: M or J outside 1 .. 2^20, D < 1, an ld < D, a workspace too small or
+ *   misaligned, a null Z / mean / log_var / out.
+ * dmvae_posterior_sample: Z[i] (f32 [n][ldz]) = z_i and logq[i] (f32 [n]) = a_i, formed in double and rounded once.  eps f32 [n][ld_eps], or
+ *   NULL: Philox stream 6, step = counter, element philox_normal_at((pos0 + i) D + d).  0 <= pos0 <= 2^34.
+ * dmvae_column_stats: out (device double [3][D], 8-byte aligned) = the column means of mu, var_of_mean, mean_of_var over the n rows, in
+ *   double in a fixed order; the variance TWO-PASS (centred on the first pass's mean): a column at 1000 +- 1e-3 keeps its 1e-6
+ *   variance, an all-equal column gives exactly 0.  ws: dmvae_column_stats_ws_bytes(n, D) bytes, 8-byte aligned.  Four launches.
+ * dmvae_sum_f64: out[0] (device double, 8-byte aligned) = sum of x[0 .. n) (f32) in double, a fixed order.  One launch. */
+int64_t dmvae_mixture_logpdf_ws_bytes(int64_t M, int64_t J, int64_t D);      /* < 0: an error code */
+int dmvae_mixture_logpdf_split(int M, int J, int D);
+int dmvae_mixture_logpdf(void* stream, const float* Z, int64_t ldz, int M, int D, const float* mean, int64_t ldm, const float* log_var, int64_t ldv,
+                         int J, const float* log_w, void* ws, int64_t ws_bytes, float* out);
+int dmvae_posterior_sample(void* stream, const float* mean, int64_t ldm, const float* log_var, int64_t ldv, int n, int D, const float* eps,
+                           int64_t ld_eps, uint64_t seed, uint64_t counter, int64_t pos0, float* Z, int64_t ldz, float* logq);
+int64_t dmvae_column_stats_ws_bytes(int64_t n, int64_t D);                   /* < 0: an error code */
+int dmvae_column_stats(void* stream, const float* mean, int64_t ldm, const float* log_var, int64_t ldv, int n, int D, void* ws, int64_t ws_bytes,
+                       double* out);
+int dmvae_sum_f64(void* stream, const float* x, int64_t n, double* out);
+
 /* Measurement and tuning entry points (per-kernel timing for bench.py's roofline leg, probes, tile knobs) are
  * declared in dmvae_hip_debug.h: exported by the same library, not part of the drop-in boundary. */
 int dmvae_abi_version(void);
