@@ -497,6 +497,51 @@ class DeepMixtureVAE(VAE):
         res = density.diagnostics_from(enq, au_threshold)
         return (res, enq["z"], enq["a"]) if return_points else res
 
+    def _eval_means_device(self, data):
+        """the encoder means of `data` in its current order as one [N][latent_dim] f32 device tensor (_eval_perm then holds that order);
+        only enqueues: gather, encoder and a device copy of the "mean" view per batch"""
+        import torch
+        eng = self._engine
+        Z = torch.empty((len(data.order), self.latent_dim), dtype=torch.float32, device=self._session.device)
+        for s, n in self._eval_batches(data, data.order):
+            eng.encode(n)
+            Z[s:s + n].copy_(eng.view("mean", n))
+        return Z
+
+    def get_knn_accuracy(self, session, train_data, test_data, k=10, return_confusion=False):
+        """Are rows of one class close in latent space, whatever the clusters did with them?  The accuracy of sklearn's uniform-weight
+        k-nearest-neighbour classifier (Euclidean, brute force) fitted on the encoder means of `train_data` and asked about those of
+        `test_data`: all pairs on the GPU (dmvae_hip.knn, csrc/knn.hip), an exact distance tie going to the earlier train row in the
+        evaluated order and a tied vote to the smallest class.  Walks both data sets in their current order WITHOUT reshuffling and
+        draws nothing from the NumPy stream.  The loop only enqueues -- gather, encoder, a device copy of the means -- then the
+        neighbours, the vote, the arg-max and the count against the resident classes; the matrix and its flag come back in ONE copy.
+        return_confusion: (accuracy, the int64 matrix [predicted class][class]) instead."""
+        from dmvae_hip import knn
+        eng, dev = self._engine, self._session.device
+        n_train, n_test = len(train_data.order), len(test_data.order)
+        if not 1 <= int(k) <= min(knn.MAX_K, n_train):
+            raise ValueError("k = %d: 1 <= k <= min(%d, the %d train rows)" % (k, knn.MAX_K, n_train))
+        R = int(max(np.max(train_data._cls), np.max(test_data._cls))) + 1
+        Zx = self._eval_means_device(train_data)
+        cls_x = train_data.device_classes(dev)[self._eval_perm.long()]       # the classes of the database rows, in the evaluated order
+        Zq = self._eval_means_device(test_data)
+        conf = eng.confusion_buffer(R, dev)
+        idx, _ = knn.knn_enqueue(Zq, Zx, int(k))
+        counts, _ = knn.vote_enqueue(idx, cls_x, R, flag=conf[R * R:])
+        eng.confusion_add(conf, counts, test_data.device_classes(dev), self._eval_perm, 0, n_test)
+        d = eng.read_confusion(conf)
+        acc = float(np.trace(d)) / n_test
+        return (acc, d) if return_confusion else acc
+
+    def get_cluster_exemplars(self, session, data, n=10):
+        """The real rows that live in each cluster: an int array [n_classes][n] whose entry [c] holds the rows of `data`, in the data
+        set's own unpermuted numbering, whose encoder means are nearest prior mean c, nearest first (a tie to the row that comes
+        earlier in the current order).  No reshuffle; dmvae_hip.knn on the device, one copy back."""
+        from dmvae_hip import knn
+        Z = self._eval_means_device(data)
+        idx, _ = knn.kneighbors(self._engine.param_view("prior_means"), Z, int(n))
+        return self._eval_perm.long()[idx.long()].cpu().numpy().astype(np.int64)
+
     # ------------------------------------------------------------------ pretraining (base_models.py:304-423)
     # the variables tf.get_collection(TRAINABLE_VARIABLES, scope=name + "/encoder_network/c") returns (:313-315)
     PRIOR_VAR_LIST = ("W_ch", "b_ch", "W_logits", "b_logits")

@@ -18,6 +18,7 @@
 #include "tsne.h"
 #include "cluster_metrics.h"
 #include "mixture_density.h"
+#include "knn.h"
 #include "measure.h"
 
 namespace dmvae {
@@ -252,6 +253,19 @@ extern "C" int dmvae_column_stats(void* stream, const float* mean, int64_t ldm, 
     return column_stats_launch((hipStream_t)stream, mean, ldm, log_var, ldv, n, D, ws, ws_bytes, out);
 }
 extern "C" int dmvae_sum_f64(void* stream, const float* x, int64_t n, double* out) { return sum_f64_launch((hipStream_t)stream, x, n, out); }
+extern "C" int64_t dmvae_knn_ws_bytes(int64_t M, int64_t N, int D, int k) { return knn_ws_bytes(M, N, D, k); }
+extern "C" int dmvae_knn(void* stream, const float* Q, int64_t ldq, int M, const float* X, int64_t ldx, int N, int D, int k, int64_t self_first, void* ws,
+                         int64_t ws_bytes, int32_t* idx, float* d2, int64_t ldo) {
+    return knn_launch((hipStream_t)stream, Q, ldq, M, X, ldx, N, D, k, self_first, ws, ws_bytes, idx, d2, ldo);
+}
+extern "C" int dmvae_knn_vote(void* stream, const int32_t* idx, int64_t ldi, int M, int k, const int32_t* classes, int N, int C, float* counts, int64_t ldc,
+                              int32_t* err_flag) {
+    return knn_vote_launch((hipStream_t)stream, idx, ldi, M, k, classes, N, C, counts, ldc, err_flag);
+}
+extern "C" int dmvae_knn_ranks(void* stream, const float* X, int64_t ldx, int N, int D, const int32_t* idx, int64_t ldi, int k, int32_t* ranks, int64_t ldr,
+                               int32_t* err_flag) {
+    return knn_ranks_launch((hipStream_t)stream, X, ldx, N, D, idx, ldi, k, ranks, ldr, err_flag);
+}
 extern "C" int dmvae_recon_nblocks(int B_pad, int I_pad) { return recon_nblocks(B_pad, I_pad); }
 extern "C" int dmvae_recon_fwd_bwd(void* stream, int act_dtype, int recon_kind, int B, int B_pad, int I, int I_pad, const float* logits,
                                    int64_t ldl, const float* x, int64_t ldx, float inv_B, void* dl, int64_t ldd, float* partials) {

@@ -112,3 +112,9 @@ class TSNE:
 
     def fit_transform(self, X):
         return self.fit(X).embedding_
+
+    def trustworthiness(self, X, n_neighbors=5):
+        """sklearn.manifold.trustworthiness(X, embedding_, n_neighbors=...) of the fitted scatter, both all-pairs halves on the device
+        (dmvae_hip.knn.trustworthiness on embedding_device_): how far the neighbourhoods it draws are neighbourhoods of X"""
+        from .knn import trustworthiness
+        return trustworthiness(X, self.embedding_device_, n_neighbors)

@@ -189,6 +189,14 @@ class MoE:
         n_classes = int(np.max(data._cls)) + 1
         return self.vae._cluster_metrics(data, max(self.n_experts, n_classes), silhouette, counter, return_labels)
 
+    def get_knn_accuracy(self, session, train_data, test_data, k=10, return_confusion=False):
+        """kNN accuracy of the gate's encoder means (DeepMixtureVAE.get_knn_accuracy).  No reshuffle."""
+        return self.vae.get_knn_accuracy(session, train_data, test_data, k=k, return_confusion=return_confusion)
+
+    def get_cluster_exemplars(self, session, data, n=10):
+        """The rows of `data` nearest each expert's prior mean (DeepMixtureVAE.get_cluster_exemplars).  No reshuffle."""
+        return self.vae.get_cluster_exemplars(session, data, n=n)
+
     def predict(self, X):
         """(reconstructed_Y, reconstructed_Y_soft) of models.py:83-108 for the rows X (regression: the prediction twice)"""
         import torch

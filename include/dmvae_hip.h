@@ -710,6 +710,36 @@ int dmvae_column_stats(void* stream, const float* mean, int64_t ldm, const float
                        double* out);
 int dmvae_sum_f64(void* stream, const float* x, int64_t n, double* out);
 
+/* ---- exact k-nearest neighbours on the device (csrc/knn.hip): kNN accuracy of the encoder means, the data rows nearest
+ * a prior mean, the trustworthiness of an embedding.  The reference has none of it.  One distance and one order throughout:
+ *   d2(i, j) = acc after  acc = fmaf(q_ic - x_jc, q_ic - x_jc, acc),  c = 0 .. D - 1 ascending, f32 differences, acc starting at 0 (no norm
+ *              expansion: near rows do not cancel);  pairs of one query are ordered by (d2, j) ascending, a TOTAL order: an exact tie goes
+ *              to the lower row.  The inputs are finite.
+ * dmvae_knn: idx[i][0 .. k) (device int32 [M][ldo]) and d2[i][0 .. k) (f32 [M][ldo]) = the k rows of X [N][ldx] nearest row i of Q [M][ldq] in that
+ *   order and their d2; D columns are used, what lies between the rows is not read, and nothing outside the k columns is written.
+ *   self_first >= 0 leaves row self_first + i of X out of query i's neighbours (self-kNN, also of a slice of the queries); < 0 leaves nothing
+ *   out.  Because the order is total the result is a function of the inputs alone.  ws: the caller's scratch of dmvae_knn_ws_bytes(M, N, D, k)
+ *   bytes (host arithmetic; 0 when the queries alone fill the device: ws may then be NULL), 8-byte aligned.  One or two launches.
+ *   DMVAE_EINVAL: M or N outside 1 .. 2^20, D < 1, k outside 1 .. 256, k > N - (self_first >= 0 ? 1 : 0), ldq < D, ldx < D, ldo < k, a workspace
+ *   too small or misaligned, a null Q / X / idx / d2.
+ * dmvae_knn_vote: counts[i][c] (f32 [M][ldc], c < C) = the number of query i's k neighbours idx[i][0 .. k) (int32 [M][ldi]) whose class
+ *   classes[idx] (device int32 [N]) is c: exact small integers, so dmvae_argmax_labels on the counts is the uniform-weight vote (the smallest
+ *   class among the tied ones) and dmvae_confusion_add takes them as scores.  An index outside [0, N) or a class outside [0, C) sets bit 0 of
+ *   *err_flag (device int32, OR-ed into), checked before it indexes anything, and that neighbour counts nowhere.  1 <= C <= 4096, ldc >= C,
+ *   ldi >= k.  One launch.
+ * dmvae_knn_ranks: ranks[i][t] (int32 [N][ldr]) = #{l != i: (d2(i, l), l) < (d2(i, j), j)}, j = idx[i][t] (int32 [N][ldi], t < k): the 0-based rank of
+ *   row j among row i's neighbours in X [N][ldx], all pairs -- the all-pairs half of sklearn.manifold.trustworthiness.  An index outside
+ *   [0, N) or equal to i sets bit 0 of *err_flag and gets rank -1.  2 <= N <= 2^20, 1 <= k <= min(256, N - 1).  One launch.
+ * All three only enqueue and never synchronise; every argument is checked before anything is enqueued (DMVAE_EINVAL with the error text
+ * set); every index into the rows is 64-bit; no float atomics: two calls on the same inputs return the same bits. */
+int64_t dmvae_knn_ws_bytes(int64_t M, int64_t N, int D, int k);             /* < 0: an error code */
+int dmvae_knn(void* stream, const float* Q, int64_t ldq, int M, const float* X, int64_t ldx, int N, int D, int k, int64_t self_first, void* ws,
+              int64_t ws_bytes, int32_t* idx, float* d2, int64_t ldo);
+int dmvae_knn_vote(void* stream, const int32_t* idx, int64_t ldi, int M, int k, const int32_t* classes, int N, int C, float* counts, int64_t ldc,
+                   int32_t* err_flag);
+int dmvae_knn_ranks(void* stream, const float* X, int64_t ldx, int N, int D, const int32_t* idx, int64_t ldi, int k, int32_t* ranks, int64_t ldr,
+                    int32_t* err_flag);
+
 /* Measurement and tuning entry points (per-kernel timing for bench.py's roofline leg, probes, tile knobs) are
  * declared in dmvae_hip_debug.h: exported by the same library, not part of the drop-in boundary. */
 int dmvae_abi_version(void);
