@@ -397,6 +397,58 @@ extern "C" int dmvae_debug_conv_dw(void* stream, int dtype, int rows, int conv_p
     return conv_layer_dw((hipStream_t)stream, dtype, rows, conv_p, conv_c, kdim, X, ldx, dY, ldy, N, n_valid, split, slab, dW, db);
 }
 
+// ---- step_finalize and the rider launches on caller-owned buffers (tests/test_gpu_step_finalize.py): thin wrappers over the launchers the pass uses
+static int debug_finalize_args(const dmvae_debug_finalize* f, const char* who, dmvae_finalize_args* out) {
+    DMVAE_REQUIRE(f && f->rp && f->lp && f->state && f->nr >= 0 && f->nl >= 0 && f->nblk >= 0 && f->ncol >= 0 && (f->ncol == 0 || (f->part && f->gout)),
+                  "%s: step_finalize arguments: null pointer or negative count", who);
+    *out = step_finalize_args(f->rp, f->nr, f->lp, f->nl, f->inv_B, f->state, f->bump_adam, f->b1, f->b2, f->part, f->nblk, f->ncol, f->gout);
+    return 0;
+}
+extern "C" int dmvae_debug_step_finalize(void* stream, const dmvae_debug_finalize* fin) {
+    dmvae_finalize_args f;
+    TRY(debug_finalize_args(fin, "dmvae_debug_step_finalize", &f));
+    return step_finalize_launch((hipStream_t)stream, f.rp, f.nr, f.lp, f.nl, f.inv_B, f.st, f.bump_adam, f.b1, f.b2, f.part, f.nblk, f.ncol, f.gout);
+}
+extern "C" int dmvae_debug_gemm_dx_riders(void* stream, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, const dmvae_epilogue* epi,
+                                          const dmvae_debug_finalize* fin, const dmvae_debug_gather* gat, int ngat, int gat_last) {
+    DMVAE_REQUIRE(epi && (epi->kind == DMVAE_EPI_LATENT || epi->kind == DMVAE_EPI_RELU_MASK), "dmvae_debug_gemm_dx_riders: the LATENT or RELU_MASK epilogue");
+    DMVAE_REQUIRE(fin || gat, "dmvae_debug_gemm_dx_riders: no riders (use dmvae_gemm)");
+    DMVAE_REQUIRE(gat ? (ngat > 0 && ngat % 8 == 0) : ngat == 0, "dmvae_debug_gemm_dx_riders: ngat=%d: a positive multiple of 8 with a gather, 0 without", ngat);
+    DMVAE_REQUIRE(!(fin && gat && gat->state), "dmvae_debug_gemm_dx_riders: step_finalize advances the batch cursor a gather addressed through the state reads: not in one launch");
+    GemmArgs a;
+    TRY(gemm_checked((hipStream_t)stream, DMVAE_BF16, DMVAE_GEMM_DX, M, N, K, A, lda, B, ldb, epi, 1, &a));
+    GemmRiders r{};
+    if (fin) {
+        TRY(debug_finalize_args(fin, "dmvae_debug_gemm_dx_riders", &r.fin));
+        r.nfin = (r.fin.nblocks + 7) & ~7;
+    }
+    if (gat) {
+        DMVAE_REQUIRE(gat->data && gat->out_bf16 && gat->n_rows >= 0 && gat->dim > 0 && gat->B_pad > 0 && gat->n_valid >= 0 && gat->n_valid <= gat->B_pad &&
+                      gat->ld % 4 == 0 && gat->ld >= gat->dim && (int64_t)gat->B_pad * (gat->ld / 4) < (int64_t(1) << 31) - int64_t(512) * 512 * 16,
+                      "dmvae_debug_gemm_dx_riders: gather arguments (ld a multiple of 4, >= dim; n_valid <= B_pad; B_pad x ld within 32-bit quad indices)");
+        r.gat = gather_args(DMVAE_BF16, gat->data, gat->n_rows, gat->dim, gat->perm, gat->first, gat->batch, gat->n_valid, gat->B_pad, gat->out_bf16, gat->ld,
+                            nullptr, gat->ld, (int)gat->ld, gat->state);
+        r.ngat = ngat;
+        r.gat_last = gat_last ? 1 : 0;
+    }
+    DMVAE_REQUIRE(gemm_bf16_riders_room(a, false) >= r.nfin + r.ngat, "dmvae_debug_gemm_dx_riders: %d rider ids, the launch has room for %d (-1: not a small-tile launch)",
+                  r.nfin + r.ngat, gemm_bf16_riders_room(a, false));
+    DMVAE_REQUIRE(!fin || gemm_bf16_carries_finalize(a), "dmvae_debug_gemm_dx_riders: the two-wave 16-row tile cannot carry the step_finalize blocks");
+    return gemm_bf16_dispatch((hipStream_t)stream, DMVAE_GEMM_DX, a, 1, &r);
+}
+extern "C" int dmvae_debug_gemm_grouped_fin(void* stream, const dmvae_gemm_problem* probs, int n, const dmvae_debug_finalize* fin) {
+    DMVAE_REQUIRE(probs && n >= 1 && n <= DMVAE_MAX_GROUP, "dmvae_debug_gemm_grouped_fin: 1..%d problems", DMVAE_MAX_GROUP);
+    dmvae_finalize_args f;
+    TRY(debug_finalize_args(fin, "dmvae_debug_gemm_grouped_fin", &f));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<GemmArgs> q(n);
+    for (int i = 0; i < n; ++i) {
+        const dmvae_gemm_problem& pr = probs[i];
+        TRY(gemm_checked(s, DMVAE_BF16, DMVAE_GEMM_DX, pr.M, pr.N, pr.K, pr.A, pr.lda, pr.B, pr.ldb, &pr.epi, 1, &q[i]));
+    }
+    return gemm_bf16_grouped(s, DMVAE_GEMM_DX, q.data(), n, &f);
+}
+
 extern "C" int dmvae_prof_enable(int on) {
     std::lock_guard<std::mutex> lk(g_prof_mu);
     g_prof_on = on != 0;

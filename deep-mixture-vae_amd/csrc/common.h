@@ -134,6 +134,12 @@ struct dmvae_finalize_args {
 // order, then the 16 groups are added in ascending order.  256 threads; red = 16 x 17 floats of LDS.
 __device__ __forceinline__ void step_finalize_block(const int blk, const dmvae_finalize_args& f, float (*red)[17]) {
     if (blk == 0) {
+        // plain operators under contract(off), as adam_elem: this function is inlined into five kernels (step_finalize_kernel, the dense dX
+        // GEMM with riders, the grouped dX tiles, heads_dx.hip), and every multiply below feeds an add -- sum * inv_B into klc + klz and into
+        // recon + ..., kl_ratio * (..), x * epoch_weight -- which each of them may or may not contract into an FMA (hipcc fused
+        // csum * inv_B + klz and rsum * inv_B + kl_ratio * t: neither of the roundings the source spells).  One rounding per operator, in
+        // every home: tests/helpers/finalize_oracle.py restates these lines.
+#pragma clang fp contract(off)
         float a = 0.f, z = 0.f, c = 0.f;
         for (int i = threadIdx.x; i < f.nr; i += 256) a += f.rp[i];
         for (int i = threadIdx.x; i < f.nl; i += 256) { z += f.lp[2 * i]; c += f.lp[2 * i + 1]; }

@@ -213,10 +213,10 @@ int adam_finish_launch(hipStream_t s, void* st) {
 
 // ---------------------------------------------------------------- column sums
 // out[n] = sum_m in[m][n].  Two passes in a fixed order (no atomics):
-//   pass 1: grid (N/256-col strips) x (row slabs of 256 rows): each thread sums
-//           its column over the slab (coalesced across the 256 lanes) -> ws[slab][n]
+//   pass 1: grid (N/256-col strips) x (at most 64 row slabs of ceil(M / 64) rows, 8 at least): each thread
+//           sums its column over the slab (coalesced across the 256 lanes) -> ws[slab][n]
 //   pass 2: each thread sums its column over the slabs.
-// When M <= 256 a single pass writes out directly.
+// When M <= 64 a single pass writes out directly.
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* in, int64_t ld, int M, int N, int rows_per_slab, float* out, int64_t ldo) {
     const int n = blockIdx.x * 256 + threadIdx.x;

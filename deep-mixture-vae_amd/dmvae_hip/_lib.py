@@ -50,6 +50,7 @@ EXPORTS = [
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
     "dmvae_debug_conv_first_fwd", "dmvae_debug_conv_first_dw", "dmvae_debug_zero_border", "dmvae_debug_maxpool2_fwd", "dmvae_debug_maxpool2_bwd_relu",
     "dmvae_debug_conv_wflip", "dmvae_debug_conv_gemm", "dmvae_debug_conv_dw",
+    "dmvae_debug_step_finalize", "dmvae_debug_gemm_dx_riders", "dmvae_debug_gemm_grouped_fin",
 ]
 
 
@@ -150,6 +151,17 @@ class State(C.Structure):
         ("epoch_loss", C.c_float), ("epoch_recon", C.c_float), ("epoch_klz", C.c_float), ("epoch_klc", C.c_float),
         ("last_loss", C.c_float), ("last_recon", C.c_float), ("last_klz", C.c_float), ("last_klc", C.c_float),
     ]
+
+
+class DebugFinalize(C.Structure):      # dmvae_debug_finalize (include/dmvae_hip_debug.h)
+    _fields_ = [("rp", C.c_void_p), ("nr", C.c_int), ("lp", C.c_void_p), ("nl", C.c_int),
+                ("inv_B", C.c_float), ("state", C.c_void_p), ("bump_adam", C.c_int), ("b1", C.c_float), ("b2", C.c_float),
+                ("part", C.c_void_p), ("nblk", C.c_int), ("ncol", C.c_int), ("gout", C.c_void_p)]
+
+
+class DebugGather(C.Structure):        # dmvae_debug_gather
+    _fields_ = [("data", C.c_void_p), ("n_rows", C.c_int64), ("dim", C.c_int), ("perm", C.c_void_p), ("first", C.c_int64),
+                ("batch", C.c_int), ("n_valid", C.c_int), ("B_pad", C.c_int), ("out_bf16", C.c_void_p), ("ld", C.c_int64), ("state", C.c_void_p)]
 
 
 class Config(C.Structure):
@@ -287,6 +299,9 @@ def _load():
         "dmvae_debug_conv_wflip": [vp, i32, vp, i32, i32, i32, i32, vp, i32],
         "dmvae_debug_conv_gemm": [vp, i32, i32, i32, i32, i32, vp, i64, vp, i64, P(Epilogue), i32, i32, i32],
         "dmvae_debug_conv_dw": [vp, i32, i32, i32, i32, vp, i64, vp, i64, i32, i32, i32, vp, vp, vp],
+        "dmvae_debug_step_finalize": [vp, P(DebugFinalize)],
+        "dmvae_debug_gemm_dx_riders": [vp, i32, i32, i32, vp, i64, vp, i64, P(Epilogue), P(DebugFinalize), P(DebugGather), i32, i32],
+        "dmvae_debug_gemm_grouped_fin": [vp, P(GemmProblem), i32, P(DebugFinalize)],
         "dmvae_abi_version": [],
         "dmvae_last_error": [],
     }

@@ -7,7 +7,9 @@
  * tests/test_gpu_gemm_forms.py forces every tile form of the dense GEMMs through dmvae_debug_set_tile and knobs 0 / 1 / 7 / 9 (and 2 / 13 / 18),
  * checks with dmvae_prof_* which instantiation ran, and holds every fused epilogue on it to an exact reference;
  * tests/test_gpu_dw_adam_forms.py does the same for the fused weight-gradient + Adam epilogue (dmvae_gemm_grouped_dw_adam): knobs 2 and 6 (and 1)
- * force each small tile and the 256x256 macro tile alone, dmvae_prof_* says which kernel families ran and how often.
+ * force each small tile and the 256x256 macro tile alone, dmvae_prof_* says which kernel families ran and how often;
+ * tests/test_gpu_step_finalize.py runs step_finalize and the batch gather in every kernel that carries them (dmvae_debug_step_finalize,
+ * dmvae_debug_gemm_dx_riders, dmvae_debug_gemm_grouped_fin) and holds them, and the GEMM under them, to exact references.
  */
 #ifndef DMVAE_HIP_DEBUG_H
 #define DMVAE_HIP_DEBUG_H
@@ -81,8 +83,11 @@ int dmvae_debug_set_tile(int bm, int bn);
  *                       on the grouped tiles (0): the pair alone 20.4 -> 17.4 us at 4096 rows, 80.3 -> 76.8 us at 16384; step -0.6 % at 16384 rows,
  *             knob 14 = blocks the latent kernel's geometry aims at (512; rows per block = 16 .. 64).  The plan sizes its partial sums for the largest
  *                       count and takes the count at enqueue time, so it may change while a plan exists.  1024 at 16384 rows: 0.9500 vs 0.9493 ms,
- *             knob 16 = where the step_finalize blocks run: 1 (default) as riders of the dZ GEMM while tiles + riders <= 256 (4096 rows), else of the
- *                       heads' dX launch; 2 always the heads' dX launch; 0 a launch of their own (0.2796 vs 0.2753 ms at 4096 rows),
+ *             knob 16 = where the step_finalize blocks run: 1 (default) as riders of the dZ GEMM while tiles + riders <= 256 and its tile has four waves
+ *                       (the 64- and 32-row tiles), else as second workgroups of the output layer's dX launch while tiles + riders <= 512 (where they
+ *                       also go when a prefetched batch's gather rides in the dZ GEMM), else of the heads' dX launch; 2 always the heads' dX launch;
+ *                       3 the output layer's dX launch whenever it has the room, else the heads' dX launch (0.2717 vs 0.2721 ms at 4096 rows);
+ *                       0 a launch of their own (0.2796 vs 0.2753 ms at 4096 rows),
  *             knob 17 = where the gather of a prefetched batch (dmvae_plan_prefetch_batch) runs: 1 (default) on the idle CUs of the dZ GEMM, one block
  *                       each, in the last ids of its grid (12.98 us for that launch at 4096 rows, 11.2 without riders); 2 the same in the first ids
  *                       (14.1 us); 3 two blocks per idle CU, last ids (15.5 us); 0 a launch of its own in front of the trunk's backward pass.
@@ -131,6 +136,42 @@ int dmvae_debug_conv_gemm(void* stream, int dtype, int layout, int M, int N, int
  * (split * (pad64(9 * conv_c) + 1) * N floats) added in a fixed order; the pad rows past the ninth tap are zeroed */
 int dmvae_debug_conv_dw(void* stream, int dtype, int rows, int conv_p, int conv_c, const void* X, int64_t ldx, const void* dY, int64_t ldy,
                         int N, int n_valid, int split, float* slab, float* dW, float* db);
+
+/* ---- step_finalize and the rider launches on caller-owned buffers (csrc/common.h step_finalize_block, csrc/gemm_epilogue.h gather_rows_block;
+ * tests/test_gpu_step_finalize.py) ----------
+ * step_finalize_block is compiled into five kernels: its own, the dense dX GEMM that carries riders (LATENT = the dZ GEMM, RELU_MASK = a layer's dX),
+ * the grouped dX tiles and the streaming dX of the head layers; gather_rows_block into its own kernel and the dense dX GEMM.  The step picks the home
+ * by shape and knobs (csrc/step.hip place_riders); these entries reach every home on buffers of the caller's.
+ * rp = nr reconstruction-loss partials, lp = nl pairs {kl_z, kl_c}, state = a dmvae_state on the device (read and written), part = [nblk][ncol] prior-table
+ * gradient partials -> gout[ncol]; bump_adam: advance adam_t and write lr_t (b1, b2). */
+typedef struct dmvae_debug_finalize {
+    const float* rp; int nr;
+    const float* lp; int nl;
+    float inv_B; void* state; int bump_adam;
+    float b1, b2;
+    const float* part; int nblk, ncol;
+    float* gout;
+} dmvae_debug_finalize;
+/* the arguments of dmvae_gather_rows with a bf16 output only: out_bf16 = [B_pad][ld], every column written (pad rows and columns: zeros) */
+typedef struct dmvae_debug_gather {
+    const float* data; int64_t n_rows; int dim;
+    const int32_t* perm; int64_t first;
+    int batch, n_valid, B_pad;
+    void* out_bf16; int64_t ld;
+    const void* state;
+} dmvae_debug_gather;
+/* the stand-alone kernel (1 + ceil(ncol / 16) workgroups) */
+int dmvae_debug_step_finalize(void* stream, const dmvae_debug_finalize* fin);
+/* dmvae_gemm(bf16, DMVAE_GEMM_DX, LATENT | RELU_MASK epilogue, no K split) with riders in its grid: the step_finalize blocks in the first
+ * (nblocks + 7) & ~7 ids (fin, may be NULL) and / or ngat workgroups of the gather (gat, may be NULL; ngat a multiple of 8) behind them, or --
+ * gat_last -- in the last ids of the grid.  DMVAE_EINVAL: ngat not a multiple of 8; a launch without the room (small dense tiles only, tiles + riders
+ * <= 512); fin on the two-wave 16-row tile of the dZ GEMM; fin together with a gather addressed through the state's batch cursor (finalize advances
+ * the cursor the gather reads: the step never puts the two into one launch). */
+int dmvae_debug_gemm_dx_riders(void* stream, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, const dmvae_epilogue* epi,
+                               const dmvae_debug_finalize* fin, const dmvae_debug_gather* gat, int ngat, int gat_last);
+/* dmvae_gemm_grouped(bf16, DMVAE_GEMM_DX) of RELU_MASK problems with the step_finalize blocks riding: on the streaming kernel where it takes the group
+ * (csrc/heads_dx.hip, knob 13), else on the grouped tiles */
+int dmvae_debug_gemm_grouped_fin(void* stream, const dmvae_gemm_problem* probs, int n, const dmvae_debug_finalize* fin);
 
 #ifdef __cplusplus
 }

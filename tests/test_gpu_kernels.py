@@ -560,16 +560,23 @@ def test_recon_standalone(hip, act):
 
 
 def test_colsum(hip):
+    """(M, N, dtype, ld): M = 1 / 64 / 65 are the single-pass form (up to 64 rows) at its ends and the first two-pass shape (slabs of 8 rows, a last
+    slab of one); ld > N with NaN in the pad columns (a column past N read shows); N below, at and above a multiple of the 256-column strips;
+    the output's guard band stays as it was"""
     L = hip
     rng = np.random.RandomState(2)
-    for (M, N, dt) in [(100, 70, 0), (4096, 832, 1), (513, 300, 0), (8192, 64, 1)]:
+    for (M, N, dt, ld) in [(100, 70, 0, 70), (4096, 832, 1, 832), (513, 300, 0, 300), (8192, 64, 1, 64),
+                           (1, 70, 0, 96), (1, 256, 1, 264), (64, 257, 1, 272), (64, 70, 0, 70), (65, 257, 0, 260), (65, 513, 1, 520), (100, 255, 1, 256)]:
         a = rng.randn(M, N)
-        ad = dev(a, _act(dt))
-        out = torch.zeros(N, dtype=torch.float32, device="cuda")
-        L.check(L.lib.dmvae_colsum(stream(), dt, L.ptr(ad), N, M, N, L.ptr(out)))
+        full = np.full((M, ld), np.nan)
+        full[:, :N] = a
+        ad = dev(full, _act(dt))
+        out = torch.full((N + 64,), 7.0, dtype=torch.float32, device="cuda")
+        L.check(L.lib.dmvae_colsum(stream(), dt, L.ptr(ad), ld, M, N, L.ptr(out)))
         torch.cuda.synchronize()
-        ref = ad.double().sum(0).cpu().numpy()
-        np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=2e-5, atol=2e-4)
+        ref = ad[:, :N].double().sum(0).cpu().numpy()
+        np.testing.assert_allclose(out[:N].cpu().numpy(), ref, rtol=2e-5, atol=2e-4, err_msg=str((M, N, dt, ld)))
+        assert bool((out[N:] == 7.0).all()), (M, N, dt, ld)
 
 
 # bf16 mode (hardware sqrt / reciprocal, 1 ulp each) | bf16 mode with DMVAE_ADAM_IEEE (dmvae_config.adam_ieee) | fp32 parity mode (IEEE)
@@ -666,6 +673,80 @@ def test_gather_rows_follows_dataset_order(hip):
             exp[:nv, :dim] = data[perm[first:first + nv]]
             np.testing.assert_array_equal(of.cpu().numpy(), exp)
             np.testing.assert_array_equal(oa.float().cpu().numpy(), torch.as_tensor(exp).to(_act(act)).float().numpy())
+
+
+def _gather_expected(data, perm, first, nv, Bp, ld):
+    """row r < nv = data[perm[first + r]] where first + r and the entry lie inside the data set, else zeros; pad rows and columns zeros"""
+    N, dim = data.shape
+    exp = np.zeros((Bp, ld), np.float32)
+    src = first + np.arange(nv)
+    ok = (src >= 0) & (src < N)
+    idx = np.where(ok, perm[np.clip(src, 0, N - 1)].astype(np.int64), -1)
+    ok &= (idx >= 0) & (idx < N)
+    exp[np.nonzero(ok)[0], :dim] = data[idx[ok]]
+    return exp
+
+
+def _gather_run(L, act, dd, N, dim, pd, first, B, nv, Bp, ld):
+    """-> (act copy, f32 copy) of one dmvae_gather_rows call, each [Bp][ld] between guard bands that must come back untouched"""
+    G = 4096
+    oa = torch.full((2 * G + Bp * ld,), 7.0, dtype=_act(act), device="cuda")
+    of = torch.full((2 * G + Bp * ld,), 7.0, dtype=torch.float32, device="cuda")
+    L.check(L.lib.dmvae_gather_rows(stream(), act, L.ptr(dd), N, dim, L.ptr(pd), first, B, nv, Bp,
+                                    C.c_void_p(oa.data_ptr() + G * oa.element_size()), ld, C.c_void_p(of.data_ptr() + G * 4), ld, None))
+    torch.cuda.synchronize()
+    for o in (oa, of):
+        assert bool((o[:G] == 7.0).all()) and bool((o[-G:] == 7.0).all()), "the gather wrote outside [B_pad][ld]"
+    return oa[G:-G].view(Bp, ld), of[G:-G].view(Bp, ld)
+
+
+# (dim, B_pad, ld): ld > dim, and B_pad * ld / 4 quads no multiple of the 2048 a block takes per pass: 100, 2176 and 39 936
+@pytest.mark.parametrize("dim,Bp,ld", [(4, 100, 4), (20, 128, 68), (784, 192, 832)])
+def test_gather_rows_fast_path_and_its_misaligned_twin(hip, dim, Bp, ld):
+    """input_dim a multiple of 4 on a 16-byte aligned data set: the 16-byte loads every real data set takes.  The same data through a view
+    4 bytes further on takes the element-wise path: identical results.  A batch that runs past the data set and permutation entries outside
+    it give zero rows; pad rows and pad columns are zeros; nothing is written outside [B_pad][ld]."""
+    L = hip
+    rng = np.random.RandomState(dim)
+    N, B = 300, 100
+    data = rng.rand(N, dim).astype(np.float32) + np.float32(0.25)          # no zero: a row of zeros is a row that was not fetched
+    perm = rng.permutation(N).astype(np.int32)
+    perm[[7, 50, 120, 299]] = [N, -1, 2 ** 31 - 1, -2 ** 31]
+    flat = torch.zeros(N * dim + 4, dtype=torch.float32, device="cuda")
+    assert flat.data_ptr() % 16 == 0
+    aligned, shifted = flat[:N * dim].view(N, dim), flat[1:N * dim + 1].view(N, dim)
+    pd = torch.as_tensor(perm).cuda()
+    for first, nv in ((0, 100), (N - 60, 100), (N - 1, 1), (N, 100), (40, 37)):
+        exp = _gather_expected(data, perm, first, nv, Bp, ld)
+        assert nv <= Bp and (first + nv <= N or not exp[max(0, N - first):].any())
+        for act in (1, 0):
+            res = []
+            for view in (aligned, shifted):
+                flat.zero_()
+                view.copy_(torch.as_tensor(data))
+                assert (view.data_ptr() % 16 == 0) == (view is aligned)
+                oa, of = _gather_run(L, act, view, N, dim, pd, first, B, nv, Bp, ld)
+                np.testing.assert_array_equal(of.cpu().numpy(), exp, err_msg=str((dim, first, nv, act, view is aligned)))
+                np.testing.assert_array_equal(oa.float().cpu().numpy(), torch.as_tensor(exp).to(_act(act)).float().numpy())
+                res.append((oa.clone(), of.clone()))
+            assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
+
+
+def test_gather_rows_grid_stride(hip):
+    """more than 2048 x 1024 quads: the grid is capped at 2048 blocks of 1024 quads per pass, so blocks take a second pass"""
+    L = hip
+    rng = np.random.RandomState(9)
+    N, dim, Bp, ld = 8200, 1028, 8192, 1028
+    assert Bp * (ld // 4) > 2048 * 1024
+    data = rng.rand(N, dim).astype(np.float32) + np.float32(0.25)
+    perm = rng.permutation(N).astype(np.int32)
+    dd, pd = dev(data), torch.as_tensor(perm).cuda()
+    first, nv = 100, 8150                                                  # the last 50 rows of the batch lie past the data set, 42 more are pad rows
+    oa, of = _gather_run(L, 1, dd, N, dim, pd, first, Bp, nv, Bp, ld)
+    exp = _gather_expected(data, perm, first, nv, Bp, ld)
+    assert exp[:N - first].all() and not exp[N - first:].any()
+    assert torch.equal(of.cpu(), torch.as_tensor(exp))
+    assert torch.equal(oa.cpu(), torch.as_tensor(exp).to(torch.bfloat16))
 
 
 def test_philox_noise_moments_and_cast(hip):

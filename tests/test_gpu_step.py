@@ -323,6 +323,71 @@ def test_graph_replay_matches_eager_and_epoch_accounting():
     assert 100 < out[0][0] < 600          # epoch-mean loss in nats, 784*ln2 = 543 at init
 
 
+_FIN_FIELDS = ("last_loss", "last_recon", "last_klz", "last_klc", "epoch_loss", "epoch_recon", "epoch_klz", "epoch_klc", "lr_t", "adam_t", "noise_step", "batch_cursor")
+
+
+def _profiled_rows(L, fn):
+    """{profiler row: launches} of the library calls fn makes"""
+    rows = (L.ProfRow * 64)()
+    L.lib.dmvae_prof_collect(rows, 64)          # drop whatever was recorded before
+    L.lib.dmvae_prof_enable(1)
+    try:
+        fn()
+        torch.cuda.synchronize()
+    finally:
+        L.lib.dmvae_prof_enable(0)
+        n = L.lib.dmvae_prof_collect(rows, 64)
+    return {rows[i].name.decode(): int(rows[i].launches) for i in range(n)}
+
+
+@pytest.mark.parametrize("B", [256, 4096])
+def test_step_finalize_placements_leave_the_same_bits(hip, B):
+    """step_finalize_block is compiled into five kernels and knob 16 says which one a step runs it in (csrc/step.hip place_riders): 0 a launch
+    of its own, 1 the dZ GEMM where its tile carries it, else the output layer's dX, 2 the heads' dX (the streaming kernel), 3 the output
+    layer's dX.  Two train steps under each setting, the batch addressed through the device cursor: the state (loss scalars, epoch sums,
+    lr_t, the counters, the cursor), the gradient arena (the fused step writes the prior-table sums there), parameters, moments and the bf16
+    shadow are bit-identical -- a multiply-add of block 0 contracted in one kernel and not in another would show in last_loss / epoch_*.
+    The profiler's step_finalize row: one launch per step with knob 16 = 0, none otherwise.  The same with the 64-row dZ tiles (knob 18 = 0),
+    where setting 1 rides in the dZ GEMM itself."""
+    kw = dict(input_dim=784, latent_dim=64, n_classes=10)
+    X = torch.as_tensor(O.synthetic_images(2 * B, 784, seed=21)).cuda()
+    perm = torch.randperm(2 * B, device="cuda").to(torch.int32)
+    rng = np.random.RandomState(B)
+    eps = [torch.as_tensor(rng.randn(B, 64).astype(np.float32)).cuda() for _ in range(2)]
+
+    def run(knob16):
+        hip.check(hip.lib.dmvae_debug_set_knob(16, knob16))
+        e = make(kw, "bf16", B, seed=3)
+        e.reset_epoch(2, kl_ratio=0.37)
+
+        def steps():
+            for ed in eps:
+                e.train_step(X, perm, B, ed, None, 0, True)
+        rows = _profiled_rows(hip, steps)
+        assert rows.get("step_finalize", 0) == (2 if knob16 == 0 else 0), (knob16, rows)
+        st = e.read_state()
+        assert (st.adam_t, st.noise_step, st.batch_cursor) == (2, 2, 0)
+        assert e.grad_view("prior_means").abs().sum().item() > 0          # (written by the step_finalize blocks)
+        return {k: getattr(st, k) for k in _FIN_FIELDS}, [getattr(e, n).clone() for n in ("grad", "param", "m", "v", "param_bf16")]
+
+    try:
+        for knob18, settings in ((2, (0, 1, 2, 3)), (0, (0, 1))):
+            hip.check(hip.lib.dmvae_debug_set_knob(18, knob18))
+            ref = None
+            for knob16 in settings:
+                state, arenas = run(knob16)
+                if ref is None:
+                    ref = (state, arenas)
+                    assert 100 < state["last_loss"] < 700
+                    continue
+                assert state == ref[0], (B, knob18, knob16, {k: (state[k], ref[0][k]) for k in state if state[k] != ref[0][k]})
+                for name, a, b in zip(("grad", "param", "m", "v", "param_bf16"), arenas, ref[1]):
+                    assert torch.equal(a, b), (B, knob18, knob16, name, int((a != b).sum().item()))
+    finally:
+        hip.check(hip.lib.dmvae_debug_set_knob(16, 1))
+        hip.check(hip.lib.dmvae_debug_set_knob(18, 2))
+
+
 _KNOB_DEFAULTS = {1: 1, 17: 1, 18: 2}
 
 
