@@ -533,6 +533,30 @@ class DeepMixtureVAE(VAE):
         acc = float(np.trace(d)) / n_test
         return (acc, d) if return_confusion else acc
 
+    def get_linear_probe_accuracy(self, session, train_data, test_data, C=1.0, tol=1e-4, max_iter=200, standardize=True, return_confusion=False):
+        """Are the classes linearly separable in latent space?  The accuracy on `test_data` of a multinomial logistic regression (the
+        "linear probe": sklearn's LogisticRegression objective, inverse penalty C) fitted on the encoder means of `train_data`: loss and
+        gradient of every L-BFGS evaluation in one pass over the rows on the GPU (dmvae_hip.probe, csrc/probe.hip).  Where kNN is local
+        and depends on the metric, the probe is global and indifferent to an invertible linear map of z.  Walks both data sets in their
+        current order WITHOUT reshuffling and draws nothing from the NumPy stream.  standardize: the train means' column mean and
+        1 / std reach the kernels as shift and scale.  The test means' scores go to the arg-max count against the resident classes (a
+        tie to the smaller class); the matrix and its flag come back in ONE copy.  The fitted probe stays in last_linear_probe_.
+        return_confusion: (accuracy, the int64 matrix [predicted class][class]) instead."""
+        from dmvae_hip import probe
+        eng, dev = self._engine, self._session.device
+        n_test = len(test_data.order)
+        R = int(max(np.max(train_data._cls), np.max(test_data._cls))) + 1
+        Zx = self._eval_means_device(train_data)
+        cls_x = train_data.device_classes(dev)[self._eval_perm.long()]       # the classes of the fit rows, in the evaluated order
+        Zq = self._eval_means_device(test_data)
+        clf = probe.LogisticRegression(C=C, tol=tol, max_iter=max_iter, standardize=standardize, n_classes=max(R, 2)).fit(Zx, cls_x)
+        self.last_linear_probe_ = clf
+        conf = eng.confusion_buffer(max(R, 2), dev)
+        eng.confusion_add(conf, clf.decision_function(Zq), test_data.device_classes(dev), self._eval_perm, 0, n_test)
+        d = eng.read_confusion(conf)[:R, :R]
+        acc = float(np.trace(d)) / n_test
+        return (acc, d) if return_confusion else acc
+
     def get_cluster_exemplars(self, session, data, n=10):
         """The real rows that live in each cluster: an int array [n_classes][n] whose entry [c] holds the rows of `data`, in the data
         set's own unpermuted numbering, whose encoder means are nearest prior mean c, nearest first (a tie to the row that comes

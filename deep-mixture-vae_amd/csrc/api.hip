@@ -19,6 +19,7 @@
 #include "cluster_metrics.h"
 #include "mixture_density.h"
 #include "knn.h"
+#include "probe.h"
 #include "measure.h"
 
 namespace dmvae {
@@ -265,6 +266,15 @@ extern "C" int dmvae_knn_vote(void* stream, const int32_t* idx, int64_t ldi, int
 extern "C" int dmvae_knn_ranks(void* stream, const float* X, int64_t ldx, int N, int D, const int32_t* idx, int64_t ldi, int k, int32_t* ranks, int64_t ldr,
                                int32_t* err_flag) {
     return knn_ranks_launch((hipStream_t)stream, X, ldx, N, D, idx, ldi, k, ranks, ldr, err_flag);
+}
+extern "C" int64_t dmvae_softmax_xent_ws_bytes(int64_t n, int D, int C) { return probe_xent_ws_bytes(n, D, C); }
+extern "C" int dmvae_softmax_xent(void* stream, const float* Z, int64_t ldz, int64_t n, int D, const float* shift, const float* scale, const int32_t* classes,
+                                  int C, const float* W, int64_t ldw, const float* b, void* ws, int64_t ws_bytes, double* out, int32_t* flag) {
+    return probe_xent_launch((hipStream_t)stream, Z, ldz, n, D, shift, scale, classes, C, W, ldw, b, ws, ws_bytes, out, flag);
+}
+extern "C" int dmvae_linear_scores(void* stream, const float* Z, int64_t ldz, int M, int D, const float* shift, const float* scale, const float* W, int64_t ldw,
+                                   const float* b, int C, float* scores, int64_t lds) {
+    return probe_scores_launch((hipStream_t)stream, Z, ldz, M, D, shift, scale, W, ldw, b, C, scores, lds);
 }
 extern "C" int dmvae_recon_nblocks(int B_pad, int I_pad) { return recon_nblocks(B_pad, I_pad); }
 extern "C" int dmvae_recon_fwd_bwd(void* stream, int act_dtype, int recon_kind, int B, int B_pad, int I, int I_pad, const float* logits,

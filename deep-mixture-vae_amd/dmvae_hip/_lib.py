@@ -47,6 +47,7 @@ EXPORTS = [
     "dmvae_mixture_logpdf_ws_bytes", "dmvae_mixture_logpdf_split", "dmvae_mixture_logpdf", "dmvae_posterior_sample", "dmvae_column_stats_ws_bytes",
     "dmvae_column_stats", "dmvae_sum_f64",
     "dmvae_knn_ws_bytes", "dmvae_knn", "dmvae_knn_vote", "dmvae_knn_ranks",
+    "dmvae_softmax_xent_ws_bytes", "dmvae_softmax_xent", "dmvae_linear_scores",
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
     "dmvae_debug_conv_first_fwd", "dmvae_debug_conv_first_dw", "dmvae_debug_zero_border", "dmvae_debug_maxpool2_fwd", "dmvae_debug_maxpool2_bwd_relu",
     "dmvae_debug_conv_wflip", "dmvae_debug_conv_gemm", "dmvae_debug_conv_dw",
@@ -282,6 +283,9 @@ def _load():
         "dmvae_knn": [vp, vp, i64, i32, vp, i64, i32, i32, i32, i64, vp, i64, vp, vp, i64],
         "dmvae_knn_vote": [vp, vp, i64, i32, i32, vp, i32, i32, vp, i64, vp],
         "dmvae_knn_ranks": [vp, vp, i64, i32, i32, vp, i64, i32, vp, i64, vp],
+        "dmvae_softmax_xent_ws_bytes": [i64, i32, i32],
+        "dmvae_softmax_xent": [vp, vp, i64, i64, i32, vp, vp, vp, i32, vp, i64, vp, vp, i64, vp, vp],
+        "dmvae_linear_scores": [vp, vp, i64, i32, i32, vp, vp, vp, i64, vp, i32, vp, i64],
         "dmvae_prof_enable": [i32],
         "dmvae_debug_spin": [vp, i32],
         "dmvae_debug_strip_fwd2": [vp, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64],
@@ -322,6 +326,7 @@ def _load():
     lib.dmvae_mixture_logpdf_ws_bytes.restype = C.c_int64
     lib.dmvae_column_stats_ws_bytes.restype = C.c_int64
     lib.dmvae_knn_ws_bytes.restype = C.c_int64
+    lib.dmvae_softmax_xent_ws_bytes.restype = C.c_int64
     lib.dmvae_plan_destroy.restype = None
     got = lib.dmvae_abi_version()
     if got != ABI_VERSION:       # the public structs grew between versions: a mismatched pair would read past them

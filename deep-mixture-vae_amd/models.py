@@ -193,6 +193,13 @@ class MoE:
         """kNN accuracy of the gate's encoder means (DeepMixtureVAE.get_knn_accuracy).  No reshuffle."""
         return self.vae.get_knn_accuracy(session, train_data, test_data, k=k, return_confusion=return_confusion)
 
+    def get_linear_probe_accuracy(self, session, train_data, test_data, C=1.0, tol=1e-4, max_iter=200, standardize=True, return_confusion=False):
+        """Linear-probe accuracy of the gate's encoder means (DeepMixtureVAE.get_linear_probe_accuracy).  No reshuffle."""
+        res = self.vae.get_linear_probe_accuracy(session, train_data, test_data, C=C, tol=tol, max_iter=max_iter, standardize=standardize,
+                                                 return_confusion=return_confusion)
+        self.last_linear_probe_ = self.vae.last_linear_probe_
+        return res
+
     def get_cluster_exemplars(self, session, data, n=10):
         """The rows of `data` nearest each expert's prior mean (DeepMixtureVAE.get_cluster_exemplars).  No reshuffle."""
         return self.vae.get_cluster_exemplars(session, data, n=n)

@@ -18,6 +18,8 @@ New flags (defaults = reference behaviour): --batch_size, --dtype, --seed,
 --metrics (per epoch: NMI, ARI, purity and the silhouette coefficient of the test set's latent means beside the accuracy, get_cluster_metrics),
 --diagnostics (dmvae / vade, per epoch on the test set: the estimate of I(x;z), KL(q(z) || p(z)) and the active units, get_posterior_diagnostics),
 --knn K (per epoch: the accuracy of a K-nearest-neighbour vote among the train split's latent means on the test set's, get_knn_accuracy; 0 = off),
+--probe / --probe_C (per epoch: the accuracy on the test set of a linear probe -- multinomial logistic regression, inverse penalty probe_C --
+fitted on the train split's latent means, get_linear_probe_accuracy),
 --tsne (off | host | device: with --plotting, sampled.png gains the t-SNE scatter of the prior samples, embedded by sklearn on the CPU or by
 the exact t-SNE in HIP, dmvae_hip.tsne.TSNE).
 """
@@ -105,6 +107,11 @@ parser.add_argument("--knn", type=int, default=0,
                     help="K > 0 adds knnTest to the epoch line -- are rows of one class close in latent space, whatever the clusters did with them: "
                          "the accuracy on the test set of a K-nearest-neighbour vote among the encoder means of the train split, all pairs on the "
                          "device (get_knn_accuracy); rank 0 alone evaluates; 0 = off")
+parser.add_argument("--probe", action="store_true", default=False,
+                    help="adds probeTest to the epoch line -- are the classes linearly separable in latent space: the accuracy on the test set of a "
+                         "multinomial logistic regression fitted on the encoder means of the train split, loss and gradient on the device "
+                         "(get_linear_probe_accuracy); rank 0 alone evaluates")
+parser.add_argument("--probe_C", type=float, default=1.0, help="--probe: the inverse of the L2 penalty, as sklearn's C")
 parser.add_argument("--tsne", type=str, default="off", choices=["off", "host", "device"],
                     help="--plotting: add the t-SNE scatter of the prior samples (1000 per cluster) to sampled.png, embedded with sklearn on the "
                          "host (the reference's call) or with the exact t-SNE on the device (dmvae_hip.tsne.TSNE); off = the sample grid alone")
@@ -189,9 +196,12 @@ def main(argv):
     test_data = Dataset((dataset.test_data, dataset.test_classes), batch_size=argv.batch_size)
     train_data = Dataset((train_data, train_classes), batch_size=argv.batch_size)
 
-    # --knn votes among the train split alone (train_data holds the test rows too: each would find itself); unshuffled, so that
-    # nothing is drawn from the NumPy stream and the run trains as it does without the flag
-    knn_data = Dataset((dataset.train_data, dataset.train_classes), batch_size=argv.batch_size, shuffle=False) if argv.knn > 0 and rank == 0 else None
+    # --knn votes among the train split alone (train_data holds the test rows too: each would find itself) and --probe fits on it;
+    # unshuffled, so that nothing is drawn from the NumPy stream and the run trains as it does without the flags
+    split_data = (Dataset((dataset.train_data, dataset.train_classes), batch_size=argv.batch_size, shuffle=False)
+                  if (argv.knn > 0 or argv.probe) and rank == 0 else None)
+    knn_data = split_data if argv.knn > 0 else None
+    probe_data = split_data if argv.probe else None
 
     model.define_train_step(argv.init_lr, train_data.epoch_len * argv.decay_epochs, argv.decay_rate)
 
@@ -242,6 +252,7 @@ def main(argv):
             # (rank 0 alone: the call holds no collective and every rank would compute the same figures)
             pdTest = model.get_posterior_diagnostics(sess, test_data, counter=epoch) if argv.diagnostics and rank == 0 else None
             knnTest = model.get_knn_accuracy(sess, knn_data, test_data, k=argv.knn) if knn_data is not None else None
+            probeTest = model.get_linear_probe_accuracy(sess, probe_data, test_data, C=argv.probe_C) if probe_data is not None else None
             improved = accTest > maxAcc
             if world > 1:
                 # the branch below holds a COLLECTIVE (sync_master): rank 0 decides and every rank follows.  Each rank scores the same
@@ -276,6 +287,8 @@ def main(argv):
                     rec.update(_diagnostics_record(pdTest))
                 if knnTest is not None:
                     rec.update(knnTest=float(knnTest), knn_k=argv.knn)
+                if probeTest is not None:
+                    rec.update(probeTest=float(probeTest), probe_C=argv.probe_C, probe_iters=model.last_linear_probe_.n_iter_)
                 with open(argv.model + "_metrics.jsonl", "a") as fl:
                     fl.write(json.dumps(rec) + "\n")
             if math.isnan(loss):
@@ -290,6 +303,8 @@ def main(argv):
                 postfix.update(miTest="%.4f" % pdTest["mi"], auTest="%d" % pdTest["active_units"])
             if knnTest is not None:
                 postfix["knnTest"] = "%.4f" % knnTest
+            if probeTest is not None:
+                postfix["probeTest"] = "%.4f" % probeTest
             bar.set_postfix(postfix)
     if plotting:                                                  # train.py:332-334
         visualization.mnist_sample_plot(model, sess, tsne=argv.tsne != "off", tsne_backend=argv.tsne if argv.tsne != "off" else "host")
@@ -355,6 +370,7 @@ def main_moe(argv, world, rank):
         eval_seconds = time.perf_counter() - t_eval
         cmTest = model.get_cluster_metrics(sess, test_data, counter=epoch) if argv.metrics else None
         knnTest = model.get_knn_accuracy(sess, train_data, test_data, k=argv.knn) if argv.knn > 0 else None
+        probeTest = model.get_linear_probe_accuracy(sess, train_data, test_data, C=argv.probe_C) if argv.probe else None
         if accTest > maxAcc:
             maxAcc = accTest
             with open(ckpt_path + ".tmp", "wb") as f:
@@ -368,6 +384,8 @@ def main_moe(argv, world, rank):
             rec.update(_metrics_record(cmTest))
         if knnTest is not None:
             rec.update(knnTest=float(knnTest), knn_k=argv.knn)
+        if probeTest is not None:
+            rec.update(probeTest=float(probeTest), probe_C=argv.probe_C, probe_iters=model.last_linear_probe_.n_iter_)
         with open(argv.model + "_metrics.jsonl", "a") as fl:
             fl.write(json.dumps(rec) + "\n")
         print(json.dumps(rec))

@@ -740,6 +740,33 @@ int dmvae_knn_vote(void* stream, const int32_t* idx, int64_t ldi, int M, int k, 
 int dmvae_knn_ranks(void* stream, const float* X, int64_t ldx, int N, int D, const int32_t* idx, int64_t ldi, int k, int32_t* ranks, int64_t ldr,
                     int32_t* err_flag);
 
+/* ---- linear probe of the latent means on the device (csrc/probe.hip): one evaluation of the multinomial logistic
+ * regression (softmax regression) loss and gradient over all rows -- the hot path of an L-BFGS fit -- and the scores of a fitted probe.  The
+ * reference has none of it.  With u = 2^-24, Z [n][ldz] f32, classes int32 [n], W [D][ldw], b [C] (all device memory):
+ *   x_id = (Z_id - shift_d) * scale_d in f32; shift and scale (f32 [D]) are both NULL -- x is then Z bit for bit -- or both given;
+ *   l_ic = b_c + sum_d x_id W_dc, accumulated in f32 by fmaf over d ascending, starting from b_c;   m_i = max_c l_ic;
+ *   loss_i = log sum_c exp(l_ic - m_i) + m_i - l_{i, y_i}   (the log-sum-exp form: finite when the true class's probability underflows);
+ *   p_ic = exp(l_ic - m_i) / sum_c exp(l_ic - m_i);   r_ic = p_ic - [c = y_i].
+ * dmvae_softmax_xent: out (device double [1 + D C + C], 8-byte aligned, ONE buffer so that one copy brings everything back) =
+ *   out[0] = (1 / n) sum_i loss_i;  gW[d][c] = out[1 + d C + c] = (1 / n) sum_i x_id r_ic;  gb[c] = out[1 + D C + c] = (1 / n) sum_i r_ic.
+ *   No penalty term: the caller adds it in float64.  Per-row terms (x, l, p, r, loss_i) are f32; a workgroup adds its rows in ascending order
+ *   in f64, the workgroups' partials are added in f64 in a fixed order; the slabs are a function of (n, D, C) alone and there are no float
+ *   atomics, so two calls return the same bits.  A class outside [0, C) ORs bit 0 into *flag (device int32) before it indexes anything; that
+ *   row adds nothing to any sum and the divisor stays n.  ws: the caller's scratch of dmvae_softmax_xent_ws_bytes(n, D, C) bytes (host
+ *   arithmetic), 8-byte aligned.  Two launches.
+ * dmvae_linear_scores: scores[i][c] (f32 [M][lds], c < C) = l_ic of the rows of Z [M][ldz], by the device function the loss kernel uses for x
+ *   and for l: the same bits.  Nothing outside the C columns is written.  dmvae_argmax_labels on the scores is the prediction (a tie to the
+ *   smaller class) and dmvae_confusion_add takes them.  One launch.
+ * Domain: 1 <= n, M <= 2^22, 1 <= D <= 512, 2 <= C <= 256, D C <= 16384 (W and b, padded, take at most 70 KiB of LDS beside a row tile), ldz >= D,
+ *   ldw >= C, lds >= C.  Both only enqueue and never synchronise; every argument is checked before anything is enqueued (DMVAE_EINVAL with the
+ *   entry's name in the error text: outside the domain, a null Z / classes / W / b / out / flag / scores, one of shift and scale alone, a
+ *   workspace too small or misaligned); rows are indexed in 64 bits. */
+int64_t dmvae_softmax_xent_ws_bytes(int64_t n, int D, int C);               /* < 0: an error code */
+int dmvae_softmax_xent(void* stream, const float* Z, int64_t ldz, int64_t n, int D, const float* shift, const float* scale, const int32_t* classes, int C,
+                       const float* W, int64_t ldw, const float* b, void* ws, int64_t ws_bytes, double* out, int32_t* flag);
+int dmvae_linear_scores(void* stream, const float* Z, int64_t ldz, int M, int D, const float* shift, const float* scale, const float* W, int64_t ldw,
+                        const float* b, int C, float* scores, int64_t lds);
+
 /* Measurement and tuning entry points (per-kernel timing for bench.py's roofline leg, probes, tile knobs) are
  * declared in dmvae_hip_debug.h: exported by the same library, not part of the drop-in boundary. */
 int dmvae_abi_version(void);
