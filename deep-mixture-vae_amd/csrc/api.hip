@@ -459,6 +459,52 @@ extern "C" int dmvae_debug_gemm_grouped_fin(void* stream, const dmvae_gemm_probl
     return gemm_bf16_grouped(s, DMVAE_GEMM_DX, q.data(), n, &f);
 }
 
+// ---- the 256x256 macro tile with the arguments only the step sets (tests/test_gpu_gemm256_forms.py): column sums out / in, K slices into slabs
+extern "C" int dmvae_debug_gemm256(void* stream, int layout, const dmvae_debug_gemm256_problem* probs, int n, const dmvae_adam_ctx* ctx) {
+    DMVAE_REQUIRE(probs && n >= 1 && n <= DMVAE_MAX_GROUP, "dmvae_debug_gemm256: 1..%d problems", DMVAE_MAX_GROUP);
+    DMVAE_REQUIRE(layout >= 0 && layout <= 2, "dmvae_debug_gemm256: bad layout %d", layout);
+    DMVAE_REQUIRE(layout == DMVAE_GEMM_DW || n == 1, "dmvae_debug_gemm256: the FWD and DX layouts take one problem (%d given)", n);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<GemmArgs> q(n);
+    bool adam = false;
+    for (int i = 0; i < n; ++i) {
+        const dmvae_debug_gemm256_problem& d = probs[i];
+        const dmvae_gemm_problem& pr = d.p;
+        DMVAE_REQUIRE(pr.epi.recon_kind == 0 || pr.epi.recon_kind == 1, "dmvae_debug_gemm256: recon_kind %d (0 binary, 1 real)", pr.epi.recon_kind);
+        GemmArgs& a = q[i];
+        TRY(gemm_checked(s, DMVAE_BF16, layout, pr.M, pr.N, pr.K, pr.A, pr.lda, pr.B, pr.ldb, &pr.epi, 1, &a));
+        const int epi = pr.epi.kind;
+        if (!gemm_bf16_256_instantiated(layout, epi)) {
+            set_error("dmvae_debug_gemm256: layout %d with epilogue %d is not instantiated on the macro tile", layout, epi);
+            return DMVAE_EUNSUPPORTED;
+        }
+        DMVAE_REQUIRE(pr.M % 256 == 0 && pr.N % 256 == 0, "dmvae_debug_gemm256: M=%d N=%d must be multiples of 256", pr.M, pr.N);
+        const bool sums_out = (layout == DMVAE_GEMM_FWD && epi == DMVAE_EPI_BIAS_RECON) || (layout == DMVAE_GEMM_DX && epi == DMVAE_EPI_RELU_MASK);
+        DMVAE_REQUIRE(!d.csum_out || (sums_out && d.csum_ld >= pr.N && d.csum_ld % 4 == 0 && (uintptr_t)d.csum_out % 16 == 0),
+                      "dmvae_debug_gemm256: csum_out goes with FWD + BIAS_RECON / DX + RELU_MASK, 16-byte aligned, csum_ld >= N a multiple of 4");
+        DMVAE_REQUIRE(!d.csum_in || (layout == DMVAE_GEMM_DW && pr.epi.out2 && d.csum_rows >= 1 && (uintptr_t)d.csum_in % 16 == 0),
+                      "dmvae_debug_gemm256: csum_in goes with a DW problem that has a bias gradient (epi.out2), 16-byte aligned, csum_rows >= 1");
+        DMVAE_REQUIRE(!(d.csum_in && d.csum_out), "dmvae_debug_gemm256: csum_out and csum_in in one problem");
+        DMVAE_REQUIRE(d.k_split == 0 || d.k_split == pr.K || (layout == DMVAE_GEMM_DW && d.k_split > 0 && d.k_split % 64 == 0 && pr.K % d.k_split == 0),
+                      "dmvae_debug_gemm256: k_split=%d: DW layout only, a multiple of 64 that divides K=%d (0: no slices)", d.k_split, pr.K);
+        DMVAE_REQUIRE(d.slab_stride >= 0, "dmvae_debug_gemm256: negative slab_stride");
+        a.csum_out = d.csum_out; a.csum_in = d.csum_in; a.csum_ld = d.csum_ld; a.csum_rows = d.csum_rows;
+        if (d.k_split > 0) a.k_split = d.k_split;
+        a.slab_stride = d.slab_stride;
+        adam = adam || epi == DMVAE_EPI_ADAM;
+    }
+    if (adam) {      // what dmvae_gemm_grouped_dw_adam asks of its context (the segment stays with the grouped launch: none here)
+        DMVAE_REQUIRE(ctx && ctx->param && ctx->grad && ctx->m && ctx->v && ctx->state && ctx->seg_n == 0, "dmvae_debug_gemm256: DMVAE_EPI_ADAM needs a context with its arenas and state, and no extra segment");
+        for (int i = 0; i < n; ++i) {
+            DMVAE_REQUIRE(q[i].epi.kind == DMVAE_EPI_ADAM, "dmvae_debug_gemm256: one call is all DMVAE_EPI_ADAM or none");
+            const int64_t end = (reinterpret_cast<const float*>(q[i].epi.out) - ctx->grad) + (int64_t)q[i].M * q[i].epi.ldo;
+            if (end < 0 || end > (int64_t(1) << 30)) { set_error("dmvae_debug_gemm256: gradient %d ends %lld elements into the arena (limit 2^30)", i, (long long)end); return DMVAE_EUNSUPPORTED; }
+        }
+    }
+    if (layout != DMVAE_GEMM_DW) return gemm_bf16_256_launch(s, layout, q[0], nullptr);
+    return gemm_bf16_256_dw_all(s, q.data(), n, adam ? ctx : nullptr);
+}
+
 extern "C" int dmvae_prof_enable(int on) {
     std::lock_guard<std::mutex> lk(g_prof_mu);
     g_prof_on = on != 0;

@@ -421,15 +421,18 @@ void* gemm_bf16_256_anatomy() { return MEAS_SYMBOL(g_anat256); }
 static int g_policy256 = 1;     // tuning knob (dmvae_debug_set_knob 6): 0 never, 1 when the grid fills the chip, 2 whenever the shape divides
 void gemm_bf16_256_set_policy(int v) { g_policy256 = v; }
 
+bool gemm_bf16_256_instantiated(int layout, int epi) {      // the pairs gemm_bf16_256_launch has
+    return (layout == DMVAE_GEMM_FWD && (epi == DMVAE_EPI_BIAS_RELU || epi == DMVAE_EPI_BIAS_RECON || epi == DMVAE_EPI_STORE_F32)) ||
+           (layout == DMVAE_GEMM_DX && (epi == DMVAE_EPI_RELU_MASK || epi == DMVAE_EPI_STORE_F32)) ||
+           (layout == DMVAE_GEMM_DW && (epi == DMVAE_EPI_STORE_F32 || epi == DMVAE_EPI_ADAM));
+}
+
 // The 256x256 kernel takes a problem when M, N divide by 256 and the grid covers (most of) the 256 CUs; below
 // that the smaller tiles' higher workgroup count wins (gemm_bf16.hip).  K >= 512: shorter K loops do not amortise
 // the 6-half-tile prologue and the epilogue of a one-workgroup-per-CU tile.
 bool gemm_bf16_256_ok(int layout, int epi, int M, int N, int K, bool conv) {
     if (g_policy256 == 0 || conv) return false;
-    const bool inst = (layout == DMVAE_GEMM_FWD && (epi == DMVAE_EPI_BIAS_RELU || epi == DMVAE_EPI_BIAS_RECON || epi == DMVAE_EPI_STORE_F32)) ||
-                      (layout == DMVAE_GEMM_DX && (epi == DMVAE_EPI_RELU_MASK || epi == DMVAE_EPI_STORE_F32)) ||
-                      (layout == DMVAE_GEMM_DW && (epi == DMVAE_EPI_STORE_F32 || epi == DMVAE_EPI_ADAM));
-    if (!inst || M % 256 || N % 256 || K % BK) return false;
+    if (!gemm_bf16_256_instantiated(layout, epi) || M % 256 || N % 256 || K % BK) return false;
     if (g_policy256 == 2) return true;
     // K >= 1024: at K = 512 (the [z|c]-hidden layer of the MNIST-shaped configs) the two kernels tie (tools/gemm256_bench.py);
     // the dX of the narrow heads (K = 2 D or the padded class count) is the exception: N = 4096 columns of pure output

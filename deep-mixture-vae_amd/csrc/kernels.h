@@ -29,6 +29,7 @@ int gemm_bf16_tile_m(int M, int N, int split);
 int gemm_auto_group_m(int tiles_m, int tiles_n, int bm, int bn, double run = 0.0);
 // 256x256 macro-tile kernel (gemm_bf16_256.hip): takes the large dense problems, one workgroup per CU
 bool gemm_bf16_256_ok(int layout, int epi, int M, int N, int K, bool conv);
+bool gemm_bf16_256_instantiated(int layout, int epi);
 int gemm_bf16_256_launch(hipStream_t s, int layout, const GemmArgs& a, const dmvae_adam_ctx* ctx = nullptr);
 void gemm_bf16_256_set_policy(int v);
 void gemm_bf16_256_set_stagger(int v);

@@ -51,7 +51,7 @@ EXPORTS = [
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
     "dmvae_debug_conv_first_fwd", "dmvae_debug_conv_first_dw", "dmvae_debug_zero_border", "dmvae_debug_maxpool2_fwd", "dmvae_debug_maxpool2_bwd_relu",
     "dmvae_debug_conv_wflip", "dmvae_debug_conv_gemm", "dmvae_debug_conv_dw",
-    "dmvae_debug_step_finalize", "dmvae_debug_gemm_dx_riders", "dmvae_debug_gemm_grouped_fin",
+    "dmvae_debug_step_finalize", "dmvae_debug_gemm_dx_riders", "dmvae_debug_gemm_grouped_fin", "dmvae_debug_gemm256",
 ]
 
 
@@ -163,6 +163,11 @@ class DebugFinalize(C.Structure):      # dmvae_debug_finalize (include/dmvae_hip
 class DebugGather(C.Structure):        # dmvae_debug_gather
     _fields_ = [("data", C.c_void_p), ("n_rows", C.c_int64), ("dim", C.c_int), ("perm", C.c_void_p), ("first", C.c_int64),
                 ("batch", C.c_int), ("n_valid", C.c_int), ("B_pad", C.c_int), ("out_bf16", C.c_void_p), ("ld", C.c_int64), ("state", C.c_void_p)]
+
+
+class DebugGemm256Problem(C.Structure):      # dmvae_debug_gemm256_problem
+    _fields_ = [("p", GemmProblem), ("csum_out", C.c_void_p), ("csum_in", C.c_void_p), ("csum_ld", C.c_int64),
+                ("csum_rows", C.c_int), ("k_split", C.c_int), ("slab_stride", C.c_int64)]
 
 
 class Config(C.Structure):
@@ -306,6 +311,7 @@ def _load():
         "dmvae_debug_step_finalize": [vp, P(DebugFinalize)],
         "dmvae_debug_gemm_dx_riders": [vp, i32, i32, i32, vp, i64, vp, i64, P(Epilogue), P(DebugFinalize), P(DebugGather), i32, i32],
         "dmvae_debug_gemm_grouped_fin": [vp, P(GemmProblem), i32, P(DebugFinalize)],
+        "dmvae_debug_gemm256": [vp, i32, P(DebugGemm256Problem), i32, P(AdamCtx)],
         "dmvae_abi_version": [],
         "dmvae_last_error": [],
     }

@@ -9,7 +9,9 @@
  * tests/test_gpu_dw_adam_forms.py does the same for the fused weight-gradient + Adam epilogue (dmvae_gemm_grouped_dw_adam): knobs 2 and 6 (and 1)
  * force each small tile and the 256x256 macro tile alone, dmvae_prof_* says which kernel families ran and how often;
  * tests/test_gpu_step_finalize.py runs step_finalize and the batch gather in every kernel that carries them (dmvae_debug_step_finalize,
- * dmvae_debug_gemm_dx_riders, dmvae_debug_gemm_grouped_fin) and holds them, and the GEMM under them, to exact references.
+ * dmvae_debug_gemm_dx_riders, dmvae_debug_gemm_grouped_fin) and holds them, and the GEMM under them, to exact references;
+ * tests/test_gpu_gemm256_forms.py does for the 256x256 macro tile what test_gpu_gemm_forms.py does for the small tiles (knob 6 = 2), and reaches the
+ * arguments only the step sets -- column sums out / in, K slices into slabs -- through dmvae_debug_gemm256.
  */
 #ifndef DMVAE_HIP_DEBUG_H
 #define DMVAE_HIP_DEBUG_H
@@ -172,6 +174,26 @@ int dmvae_debug_gemm_dx_riders(void* stream, int M, int N, int K, const void* A,
 /* dmvae_gemm_grouped(bf16, DMVAE_GEMM_DX) of RELU_MASK problems with the step_finalize blocks riding: on the streaming kernel where it takes the group
  * (csrc/heads_dx.hip, knob 13), else on the grouped tiles */
 int dmvae_debug_gemm_grouped_fin(void* stream, const dmvae_gemm_problem* probs, int n, const dmvae_debug_finalize* fin);
+
+/* ---- the 256x256 macro tile with the arguments only the step sets (csrc/gemm_bf16_256.hip; tests/test_gpu_gemm256_forms.py) ----------
+ * bf16 problems sent to the macro tile whatever knob 6 says, each with
+ *   csum_out  FWD + BIAS_RECON / DX + RELU_MASK: the column sums of the bf16-rounded output per 256-row tile -> [M / 256][csum_ld] (NULL: none),
+ *   csum_in   DW with a bias gradient (epi.out2): such partials, [csum_rows][csum_ld] with csum_ld = N; db = their ascending sum (and its Adam
+ *             update) in the launch's extra workgroups, instead of the slab column sums of B (NULL: those),
+ *   k_split   DW + STORE_F32: K slices of this depth (a multiple of 64 that divides K), slice y -> out + y * slab_stride; 0 or K: no slices.
+ * FWD / DX: n = 1 -> gemm_bf16_256_launch; DW: n problems -> gemm_bf16_256_dw_all (merged into one grid where possible), ctx for DMVAE_EPI_ADAM.
+ * Validates like dmvae_gemm; DMVAE_EUNSUPPORTED for a (layout, epilogue) pair the macro tile is not instantiated for, DMVAE_EINVAL for a shape
+ * that does not divide by 256 x 256 x 64 and for arguments the launchers refuse (K slices with ADAM, with epi.out2 or without slab_stride;
+ * csum_ld != N on csum_in). */
+typedef struct dmvae_debug_gemm256_problem {
+    dmvae_gemm_problem p;
+    float* csum_out;
+    const float* csum_in;
+    int64_t csum_ld;
+    int csum_rows, k_split;
+    int64_t slab_stride;
+} dmvae_debug_gemm256_problem;
+int dmvae_debug_gemm256(void* stream, int layout, const dmvae_debug_gemm256_problem* probs, int n, const dmvae_adam_ctx* ctx);
 
 #ifdef __cplusplus
 }

@@ -120,9 +120,119 @@ def f32_cases():
     return [Case("f32-%s" % p.name, None, p, F32_SHAPE[0], LATENT_D if p.epi == EPI_LATENT else F32_SHAPE[1], _ks(p, F32_KS)) for p in PAIRS.values()]
 
 
+# ------------------------------------------------------------------------------------------------ the 256 x 256 macro tile
+# (csrc/gemm_bf16_256.hip; tests/test_gpu_gemm256_forms.py.  Knob 6 = 2 sends every shape that divides by 256 to it.)
+MACRO = 256
+MACRO_SHAPE = (5 * MACRO, 3 * MACRO)                    # the odd, unequal grid of the small forms: interior and edge tiles, a supertile remainder
+MACRO_PAIRS = ("fwd_bias_relu", "fwd_store", "dx_store", "dx_relu_mask", "fwd_recon_real", "dw_store_db", "fwd_recon_binary")
+MACRO_NOT_INSTANTIATED = ("fwd_bias_f32", "fwd_sigmoid", "dx_latent", "dw_atomic_s2")      # these must stay on the small tiles, exact as before
+MacroCase = collections.namedtuple("MacroCase", "id pair M N Ks rows")
+
+
+def macro_rows(pair):
+    """the profiler rows of one dmvae_gemm launch of `pair` on the macro tile (the fused bias gradient of a dW problem: slab column sums first)"""
+    rows = ["gemm_bf16_256_kernel<%d, %d>" % (pair.layout, pair.epi)]
+    return ["colsum_slabs"] + rows if pair.layout == DW else rows
+
+
+def macro_cases():
+    """every pair the macro tile is instantiated for, on 5 x 3 tiles over the K set and on a single tile with a single K tile"""
+    out = []
+    for pn in MACRO_PAIRS:
+        p = PAIRS[pn]
+        out.append(MacroCase("m256-%s" % pn, p, MACRO_SHAPE[0], MACRO_SHAPE[1], K_SET, macro_rows(p)))
+        out.append(MacroCase("m256-one-tile-%s" % pn, p, MACRO, MACRO, (64,), macro_rows(p)))
+    return out
+
+
+def macro_fallback_cases():
+    """the pairs the macro tile has no instantiation for, at a shape it would take (LATENT with a latent width of 256: out is [M][2 N])"""
+    out = []
+    for pn in MACRO_NOT_INSTANTIATED:
+        p = PAIRS[pn]
+        out.append(MacroCase("m256-not-%s" % pn, p, 2 * MACRO, MACRO, _ks(p, (64, 320)), None))
+    return out
+
+
+# column sums of the bf16-rounded output per 256-row tile (GemmArgs::csum_out), (pair, M, N, K): one, three and nine K tiles
+CSUM_OUT_CASES = tuple((pn, MACRO_SHAPE[0], MACRO_SHAPE[1], K) for pn in ("dx_relu_mask", "fwd_recon_real", "fwd_recon_binary") for K in (64, 192, 576))
+# partials handed to a weight-gradient problem (GemmArgs::csum_in): (M, N, K, csum_rows)
+CSUM_IN_CASES = ((256, 768, 128, 1), (512, 256, 192, 2), (256, 512, 320, 5))
+CSUM_IN_MERGED = (1, 2)                                 # two of them in ONE call: their bias-gradient workgroups run behind all tiles of the merged grid
+CSUM_IN_RANGE = 1000                                    # partials: integers in [-1000, 1000], nothing to do with the column sums of B
+# the chain: dY = a dx_relu_mask launch's out [M][N] and its csum_out -> B operand and csum_in of dW [CHAIN_X][N] = X^T dY over K = M rows
+CHAIN_DX = ("dx_relu_mask", MACRO_SHAPE[0], MACRO_SHAPE[1], 192)
+CHAIN_X = 256
+CHAIN_DW = (CHAIN_X, CHAIN_DX[2], CHAIN_DX[1])          # (M, N, K) of that weight-gradient problem: its operands are not a make() problem (chain_problem)
+# K slices of a weight-gradient problem into slabs: (M, N, k_split, slices).  Calls: each alone, and the three merged into one grid
+SLICE_CASES = ((512, 256, 64, 2), (256, 512, 128, 3), (256, 256, 192, 2), (256, 256, 64, 3), (256, 256, 192, 1))
+SLICE_MERGED = (0, 1, 4)                                # two sliced problems of different slice counts and one unsliced problem
+
+
+def csum_in_partials(M, N, K, rows):
+    rng = np.random.RandomState(M + 3 * N + 7 * K + rows)
+    return rng.randint(-CSUM_IN_RANGE, CSUM_IN_RANGE + 1, size=(rows, N)).astype(np.float64)
+
+
+def tile_colsums(out, valid_rows=None, valid_cols=None):
+    """float64 column sums per 256-row tile of out [M][N] -> [M / 256][N]; rows / columns at or beyond the valid counts contribute zero"""
+    o = np.array(out, dtype=np.float64)
+    if valid_rows is not None:
+        o[valid_rows:] = 0.0
+    if valid_cols is not None:
+        o[:, valid_cols:] = 0.0
+    return o.reshape(o.shape[0] // MACRO, MACRO, o.shape[1]).sum(1)
+
+
+def csum_out_expected(p):
+    """the exact column sums a macro-tile launch of p leaves: of the expected output rounded to bf16"""
+    o = bf16_round(p.expected["out"][0])
+    if p.pair.epi == EPI_BIAS_RECON:
+        return tile_colsums(o, p.m_valid, p.n_valid)
+    return tile_colsums(o)
+
+
+def colsum_exact_report(addends, tile=MACRO):
+    """the condition that makes an f32 column sum exact in ANY order: all addends of a tile's column are multiples of a common quantum q
+    (a power of two) and their absolute sum stays below 2^24 q -- every partial sum is then a multiple of q below 2^24 q: representable"""
+    a = np.abs(np.asarray(addends, dtype=np.float64))
+    nz = a[a != 0]
+    ok = {}
+    if nz.size == 0:
+        return {"(all zero)": True}
+    q = 2.0 ** np.floor(np.log2(nz.min()))
+    while not (a / q == np.rint(a / q)).all() and q > 2.0 ** -40:
+        q /= 2.0
+    ok["addends are multiples of a common quantum"] = bool((a / q == np.rint(a / q)).all())
+    rows = a.shape[0]
+    t = min(tile, rows)
+    sums = a[:rows // t * t].reshape(rows // t, t, -1).sum(1)
+    ok["sum of |addends| < 2^24 quanta per tile and column"] = bool(sums.max() < 2 ** 24 * q)
+    return ok
+
+
+def chain_problem():
+    """(the dx_relu_mask problem, X [K][CHAIN_X] as float64, dW, db): dY = the bf16-rounded expected output of the dx launch"""
+    p = make(*CHAIN_DX)
+    dY = bf16_round(p.expected["out"][0])
+    rng = np.random.RandomState(4242)
+    X = rng.randint(-2, 3, size=(p.M, CHAIN_X)).astype(np.float64)
+    return p, X, dY, X.T @ dY, dY.sum(0)
+
+
+def slice_partials(p, k_split, nsl):
+    """the exact partial product of every K slice of the dW problem p: [nsl][M][N]"""
+    return np.stack([p.A[:, y * k_split:(y + 1) * k_split] @ p.B[y * k_split:(y + 1) * k_split] for y in range(nsl)])
+
+
 def all_problem_keys():
-    """every (pair name, M, N, K) the GPU file generates: what the host test checks"""
+    """every (pair name, M, N, K) the GPU files generate: what the host test checks"""
     keys = []
+    for c in macro_cases() + macro_fallback_cases():
+        keys += [(c.pair.name, c.M, c.N, K) for K in c.Ks]
+    keys += list(CSUM_OUT_CASES) + [CHAIN_DX]
+    keys += [("dw_store_db", M, N, K) for (M, N, K, _) in CSUM_IN_CASES]
+    keys += [("dw_store_db", M, N, ks * nsl) for (M, N, ks, nsl) in SLICE_CASES]
     for c in dense_cases() + f32_cases():
         keys += [(c.pair.name, c.M, c.N, K) for K in c.Ks]
     for c in supertile_cases():
@@ -137,7 +247,7 @@ def all_problem_keys():
 
 def all_case_ids():
     return ([c.id for c in dense_cases()] + [c.id for c in supertile_cases()] + [c.id for c in THIN_CASES] + [c.id for c in grouped_cases()] +
-            [c.id for c in f32_cases()])
+            [c.id for c in f32_cases()] + [c.id for c in macro_cases()] + [c.id for c in macro_fallback_cases()])
 
 
 # ------------------------------------------------------------------------------------------------ rounding

@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hel
 import adam_exact as AX            # noqa: E402
 import finalize_oracle as FO       # noqa: E402
 import gemm_exact as GX            # noqa: E402
-from test_gpu_gemm_forms import bf16_name, collect, forced, kernels_launched, launched, setup, stream, verify      # noqa: E402
+from gemm_harness import bf16_name, collect, forced, kernels_launched, launched, setup, stream, verify             # noqa: E402
 
 F = np.float32
 

@@ -51,7 +51,8 @@ def test_ctypes_structs_match_the_header_as_a_c_compiler_lays_it_out(tmp_path):
     pairs = [("dmvae_epilogue", _lib.Epilogue), ("dmvae_gemm_problem", _lib.GemmProblem), ("dmvae_adam_ctx", _lib.AdamCtx), ("dmvae_latent_args", _lib.LatentArgs),
              ("dmvae_heads_args", _lib.HeadsArgs), ("dmvae_state", _lib.State), ("dmvae_config", _lib.Config), ("dmvae_tensor_info", _lib.TensorInfo),
              ("dmvae_sizes", _lib.Sizes), ("dmvae_buffers", _lib.Buffers), ("dmvae_prof_row", _lib.ProfRow),
-             ("dmvae_debug_finalize", _lib.DebugFinalize), ("dmvae_debug_gather", _lib.DebugGather)]
+             ("dmvae_debug_finalize", _lib.DebugFinalize), ("dmvae_debug_gather", _lib.DebugGather),
+             ("dmvae_debug_gemm256_problem", _lib.DebugGemm256Problem)]
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dmvae_hip.h")).read() + open(os.path.join(ROOT, "include", "dmvae_hip_debug.h")).read(), flags=re.S)
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "dmvae_hip_debug.h"', 'int main(void) {']
     want = {}
