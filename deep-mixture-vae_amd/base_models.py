@@ -566,6 +566,71 @@ class DeepMixtureVAE(VAE):
         idx, _ = knn.kneighbors(self._engine.param_view("prior_means"), Z, int(n))
         return self._eval_perm.long()[idx.long()].cpu().numpy().astype(np.int64)
 
+    def sample_prior_device(self, n, counter=0):
+        """(rows f32 [n][input_dim], latents f32 [n][latent_dim], components int32 [n]) on the device: decoded draws from the mixture
+        prior.  Row j comes from component c = j mod n_classes: z_j = mu_c + exp(lv_c / 2) eps_j with eps_j[d] = element j latent_dim + d
+        of the Philox stream (the model's seed, step = counter, stream id 7) of dmvae_philox_normal, and the row is the decoder's MEAN
+        image of z_j (the "recon" view), not a Bernoulli draw from it.  Only enqueues: the draw, then a decode and a device copy of
+        "recon" per batch."""
+        import torch
+        from dmvae_hip import prdc
+        eng, dev, D, K, n = self._engine, self._session.device, self.latent_dim, self.n_classes, int(n)
+        comp = torch.arange(n, device=dev) % K
+        eps = prdc.philox_normal(n * D, self.seed, step=counter, device=dev).view(n, D)
+        Z = (eng.param_view("prior_means").float()[comp] + torch.exp(eng.param_view("prior_log_vars").float()[comp] / 2) * eps).contiguous()
+        X = torch.empty((n, self.input_dim), dtype=torch.float32, device=dev)
+        for s in range(0, n, eng.max_batch):
+            b = min(eng.max_batch, n - s)
+            eng.decode(Z[s:s + b])
+            X[s:s + b].copy_(eng.view("recon", b))               # (casts a bf16 plan's view to f32)
+        return X, Z, comp.to(torch.int32)
+
+    def get_sample_quality(self, session, data, k=5, n_samples=None, space="latent", counter=0):
+        """Are the decoded draws from the mixture prior p(z) = 1/K sum_c N(mu_c, diag exp(lv_c)) realistic, and do they cover the data?
+        Improved precision and recall (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020) of M generated rows
+        against the N rows of `data`, all pairs on the GPU (dmvae_hip.prdc, csrc/prdc.hip), k-th-neighbour balls closed, squared radii
+        from dmvae_knn.  Returns dict(precision, recall, density, coverage, k, n_real, n_samples, space,
+        precision_per_cluster [K], density_per_cluster [K]) -- which component generates junk -- and, when `data` holds classes,
+        coverage_per_class and recall_per_class -- which classes the prior misses (nan for a class without rows).
+        Generated rows: M = n_samples, by default N rounded down to a multiple of K; row j comes from component j mod K (the uniform
+        prior of the KL_C term), z = mu_c + exp(lv_c / 2) eps with eps from the device's Philox stream 7 keyed by (seed, counter),
+        decoded in batches.  A generated row is the decoder's MEAN image (the "recon" view), not a Bernoulli draw from it.
+        space="latent" (default): features are encoder means -- of the real rows, and of the generated rows encoded again;
+        space="input": the rows themselves, D = input_dim.  Walks `data` in its current order WITHOUT reshuffling and draws nothing
+        from the NumPy stream; writes no parameter, moment or step state.  The loop only enqueues; one copy comes back at the end.
+        ValueError unless 1 <= k <= min(256, N - 1, M - 1) and space is one of the two."""
+        import torch
+        from dmvae_hip import prdc
+        if space not in ("latent", "input"):
+            raise ValueError("space = %r: 'latent' or 'input'" % (space,))
+        eng, dev, K, N = self._engine, self._session.device, self.n_classes, len(data.order)
+        M = (N // K) * K if n_samples is None else int(n_samples)
+        if not 1 <= int(k) <= min(256, N - 1, M - 1):
+            raise ValueError("k = %d: 1 <= k <= min(256, the %d real rows - 1, the %d generated rows - 1)" % (k, N, M))
+        X, _, comp = self.sample_prior_device(M, counter)
+        if space == "latent":
+            F = torch.empty((M, self.latent_dim), dtype=torch.float32, device=dev)
+            for s in range(0, M, eng.max_batch):
+                n = min(eng.max_batch, M - s)
+                eng.load_batch(X, None, s, n)
+                eng.encode(n)
+                F[s:s + n].copy_(eng.view("mean", n))
+            R = self._eval_means_device(data)
+        else:
+            rows = self._eval_order_on_device(data, data.order)
+            R, F = rows[self._eval_perm.long()], X
+        cls = getattr(data, "_cls", None)
+        real_groups = n_groups = None
+        if cls is not None and np.issubdtype(np.asarray(cls).dtype, np.integer) and len(cls) == len(data.order):
+            real_groups, n_groups = data.device_classes(dev)[self._eval_perm.long()], int(np.max(cls)) + 1
+        flat, layout = prdc.prdc_enqueue(R, F, int(k), real_groups, comp, n_groups, K)
+        res = prdc.prdc_from(flat, layout, N, M, int(k))
+        res["precision_per_cluster"], res["density_per_cluster"] = np.array(res.pop("precision_per_group")), np.array(res.pop("density_per_group"))
+        if real_groups is not None:
+            res["coverage_per_class"], res["recall_per_class"] = np.array(res.pop("coverage_per_group")), np.array(res.pop("recall_per_group"))
+        res.update(n_real=N, n_samples=M, space=space)
+        return res
+
     # ------------------------------------------------------------------ pretraining (base_models.py:304-423)
     # the variables tf.get_collection(TRAINABLE_VARIABLES, scope=name + "/encoder_network/c") returns (:313-315)
     PRIOR_VAR_LIST = ("W_ch", "b_ch", "W_logits", "b_logits")

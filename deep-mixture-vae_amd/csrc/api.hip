@@ -19,6 +19,7 @@
 #include "cluster_metrics.h"
 #include "mixture_density.h"
 #include "knn.h"
+#include "prdc.h"
 #include "probe.h"
 #include "measure.h"
 
@@ -266,6 +267,10 @@ extern "C" int dmvae_knn_vote(void* stream, const int32_t* idx, int64_t ldi, int
 extern "C" int dmvae_knn_ranks(void* stream, const float* X, int64_t ldx, int N, int D, const int32_t* idx, int64_t ldi, int k, int32_t* ranks, int64_t ldr,
                                int32_t* err_flag) {
     return knn_ranks_launch((hipStream_t)stream, X, ldx, N, D, idx, ldi, k, ranks, ldr, err_flag);
+}
+extern "C" int dmvae_prdc_counts(void* stream, const float* R, int64_t ldr, int N, const float* F, int64_t ldf, int M, int D, const float* rR2,
+                                 const float* rF2, int32_t* fake_in_real, int32_t* real_in_fake, float* real_min_d2, int32_t* real_min_j) {
+    return prdc_counts_launch((hipStream_t)stream, R, ldr, N, F, ldf, M, D, rR2, rF2, fake_in_real, real_in_fake, real_min_d2, real_min_j);
 }
 extern "C" int64_t dmvae_softmax_xent_ws_bytes(int64_t n, int D, int C) { return probe_xent_ws_bytes(n, D, C); }
 extern "C" int dmvae_softmax_xent(void* stream, const float* Z, int64_t ldz, int64_t n, int D, const float* shift, const float* scale, const int32_t* classes,

@@ -200,6 +200,10 @@ class MoE:
         self.last_linear_probe_ = self.vae.last_linear_probe_
         return res
 
+    def get_sample_quality(self, session, data, k=5, n_samples=None, space="latent", counter=0):
+        """Precision, recall, density and coverage of the gate's decoded prior samples (DeepMixtureVAE.get_sample_quality).  No reshuffle."""
+        return self.vae.get_sample_quality(session, data, k=k, n_samples=n_samples, space=space, counter=counter)
+
     def get_cluster_exemplars(self, session, data, n=10):
         """The rows of `data` nearest each expert's prior mean (DeepMixtureVAE.get_cluster_exemplars).  No reshuffle."""
         return self.vae.get_cluster_exemplars(session, data, n=n)

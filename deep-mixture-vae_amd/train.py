@@ -20,6 +20,8 @@ New flags (defaults = reference behaviour): --batch_size, --dtype, --seed,
 --knn K (per epoch: the accuracy of a K-nearest-neighbour vote among the train split's latent means on the test set's, get_knn_accuracy; 0 = off),
 --probe / --probe_C (per epoch: the accuracy on the test set of a linear probe -- multinomial logistic regression, inverse penalty probe_C --
 fitted on the train split's latent means, get_linear_probe_accuracy),
+--sample_quality K (per epoch on the test set: improved precision / recall and density / coverage of the decoded draws from the mixture prior,
+K-th-neighbour balls, per prior component and per class, get_sample_quality; 0 = off),
 --tsne (off | host | device: with --plotting, sampled.png gains the t-SNE scatter of the prior samples, embedded by sklearn on the CPU or by
 the exact t-SNE in HIP, dmvae_hip.tsne.TSNE).
 """
@@ -112,6 +114,11 @@ parser.add_argument("--probe", action="store_true", default=False,
                          "multinomial logistic regression fitted on the encoder means of the train split, loss and gradient on the device "
                          "(get_linear_probe_accuracy); rank 0 alone evaluates")
 parser.add_argument("--probe_C", type=float, default=1.0, help="--probe: the inverse of the L2 penalty, as sklearn's C")
+parser.add_argument("--sample_quality", type=int, default=0,
+                    help="K > 0 adds precTest and covTest to the epoch line -- are the decoded draws from the mixture prior realistic, and do they "
+                         "cover the test set: improved precision / recall and density / coverage with K-th-neighbour balls in the space of the "
+                         "encoder means, per prior component and per class in the JSONL record, all pairs on the device (get_sample_quality); "
+                         "rank 0 alone evaluates; 0 = off")
 parser.add_argument("--tsne", type=str, default="off", choices=["off", "host", "device"],
                     help="--plotting: add the t-SNE scatter of the prior samples (1000 per cluster) to sampled.png, embedded with sklearn on the "
                          "host (the reference's call) or with the exact t-SNE on the device (dmvae_hip.tsne.TSNE); off = the sample grid alone")
@@ -130,6 +137,17 @@ def _diagnostics_record(pd):
     """the JSONL keys of --diagnostics"""
     return dict(mi_test=float(pd["mi"]), marginal_kl_test=float(pd["marginal_kl"]), rate_test=float(pd["rate"]), mi_cap_test=float(pd["mi_cap"]),
                 active_units_test=int(pd["active_units"]))
+
+
+def _sample_quality_record(sq):
+    """the JSONL keys of --sample_quality (a class without rows is written as null)"""
+    vec = lambda v: [None if math.isnan(x) else float(x) for x in v]
+    rec = dict(precTest=float(sq["precision"]), recTest=float(sq["recall"]), denTest=float(sq["density"]), covTest=float(sq["coverage"]),
+               sq_k=int(sq["k"]), sq_samples=int(sq["n_samples"]), precision_per_cluster=vec(sq["precision_per_cluster"]),
+               density_per_cluster=vec(sq["density_per_cluster"]))
+    if "coverage_per_class" in sq:
+        rec.update(coverage_per_class=vec(sq["coverage_per_class"]), recall_per_class=vec(sq["recall_per_class"]))
+    return rec
 
 
 def main(argv):
@@ -253,6 +271,7 @@ def main(argv):
             pdTest = model.get_posterior_diagnostics(sess, test_data, counter=epoch) if argv.diagnostics and rank == 0 else None
             knnTest = model.get_knn_accuracy(sess, knn_data, test_data, k=argv.knn) if knn_data is not None else None
             probeTest = model.get_linear_probe_accuracy(sess, probe_data, test_data, C=argv.probe_C) if probe_data is not None else None
+            sqTest = model.get_sample_quality(sess, test_data, k=argv.sample_quality, counter=epoch) if argv.sample_quality > 0 and rank == 0 else None
             improved = accTest > maxAcc
             if world > 1:
                 # the branch below holds a COLLECTIVE (sync_master): rank 0 decides and every rank follows.  Each rank scores the same
@@ -289,6 +308,8 @@ def main(argv):
                     rec.update(knnTest=float(knnTest), knn_k=argv.knn)
                 if probeTest is not None:
                     rec.update(probeTest=float(probeTest), probe_C=argv.probe_C, probe_iters=model.last_linear_probe_.n_iter_)
+                if sqTest is not None:
+                    rec.update(_sample_quality_record(sqTest))
                 with open(argv.model + "_metrics.jsonl", "a") as fl:
                     fl.write(json.dumps(rec) + "\n")
             if math.isnan(loss):
@@ -305,6 +326,8 @@ def main(argv):
                 postfix["knnTest"] = "%.4f" % knnTest
             if probeTest is not None:
                 postfix["probeTest"] = "%.4f" % probeTest
+            if sqTest is not None:
+                postfix.update(precTest="%.4f" % sqTest["precision"], covTest="%.4f" % sqTest["coverage"])
             bar.set_postfix(postfix)
     if plotting:                                                  # train.py:332-334
         visualization.mnist_sample_plot(model, sess, tsne=argv.tsne != "off", tsne_backend=argv.tsne if argv.tsne != "off" else "host")
@@ -371,6 +394,7 @@ def main_moe(argv, world, rank):
         cmTest = model.get_cluster_metrics(sess, test_data, counter=epoch) if argv.metrics else None
         knnTest = model.get_knn_accuracy(sess, train_data, test_data, k=argv.knn) if argv.knn > 0 else None
         probeTest = model.get_linear_probe_accuracy(sess, train_data, test_data, C=argv.probe_C) if argv.probe else None
+        sqTest = model.get_sample_quality(sess, test_data, k=argv.sample_quality, counter=epoch) if argv.sample_quality > 0 else None
         if accTest > maxAcc:
             maxAcc = accTest
             with open(ckpt_path + ".tmp", "wb") as f:
@@ -386,6 +410,8 @@ def main_moe(argv, world, rank):
             rec.update(knnTest=float(knnTest), knn_k=argv.knn)
         if probeTest is not None:
             rec.update(probeTest=float(probeTest), probe_C=argv.probe_C, probe_iters=model.last_linear_probe_.n_iter_)
+        if sqTest is not None:
+            rec.update(_sample_quality_record(sqTest))
         with open(argv.model + "_metrics.jsonl", "a") as fl:
             fl.write(json.dumps(rec) + "\n")
         print(json.dumps(rec))

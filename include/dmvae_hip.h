@@ -740,6 +740,30 @@ int dmvae_knn_vote(void* stream, const int32_t* idx, int64_t ldi, int M, int k, 
 int dmvae_knn_ranks(void* stream, const float* X, int64_t ldx, int N, int D, const int32_t* idx, int64_t ldi, int k, int32_t* ranks, int64_t ldr,
                     int32_t* err_flag);
 
+/* ---- sample quality on the device (csrc/prdc.hip): the all-pairs counts behind improved precision and recall
+ * (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020) of generated rows against real rows.  The reference has none of it.
+ * R [N][ldr] holds the real rows' features, F [M][ldf] the generated rows' (f32, unit column stride, D columns used; what lies between the
+ * rows is not read).  d2(i, j) is THE distance of dmvae_knn above -- acc = fmaf(r_ic - f_jc, r_ic - f_jc, acc), f32 differences, c ascending, acc
+ * starting at 0 -- from the same tile body, so its bits are those dmvae_knn returns; negating an f32 difference is exact, so d2(R_i, F_j) and
+ * d2(F_j, R_i) are the same bits and one pass over the pairs serves both directions.  Radii are SQUARED distances and INPUTS (device f32):
+ *   rR2[i] = the d2 of R_i's k-th nearest other real row, rF2[j] the same within F: column k - 1 of dmvae_knn(X, X, k, self_first = 0).
+ * Balls are CLOSED: a pair is inside when d2 <= r2 -- the papers' definition (the `prdc` package compares with <, which differs at exact
+ * ties only).  A radius may be +inf (every pair inside) and must not be NaN: that is not checked on the device.  Outputs (device memory):
+ *   fake_in_real[j] (int32 [M]) = #{i : d2(i, j) <= rR2[i]}        real_in_fake[i] (int32 [N]) = #{j : d2(i, j) <= rF2[j]}
+ *   real_min_d2[i]  (f32 [N])   = min_j d2(i, j)                   real_min_j[i]   (int32 [N], may be NULL) = its j, the lowest on a tie
+ * from which, with the k the radii were taken at,
+ *   precision = #{j : fake_in_real[j] > 0} / M        recall   = #{i : real_in_fake[i] > 0} / N
+ *   density   = sum_j fake_in_real[j] / (k M)         coverage = #{i : real_min_d2[i] <= rR2[i]} / N.
+ * fake_in_real is zeroed on the stream, then added into with integer atomics (integer addition commutes); the minimum is an integer
+ * minimum on (d2, j) keys; there are no float atomics: two calls on the same inputs return the same bits.  One memset and one launch of
+ * ceil(N / 16) workgroups -- both sets hold thousands of rows in every use; a small N is not split.  The call only enqueues and never
+ * synchronises; every argument is checked before anything is enqueued (DMVAE_EINVAL with the entry's name in the error text: N or M outside
+ * 1 .. 2^20, D < 1, ldr < D, ldf < D, a null R / F / rR2 / rF2 / fake_in_real / real_in_fake / real_min_d2); rows are indexed in 64 bits.
+ * The model-level evaluation (get_sample_quality) draws its generated rows from Philox stream 7, step = counter,
+ * element philox_normal_at(j D + d) of generated row j: ids 0 .. 6 are taken above. */
+int dmvae_prdc_counts(void* stream, const float* R, int64_t ldr, int N, const float* F, int64_t ldf, int M, int D, const float* rR2,
+                      const float* rF2, int32_t* fake_in_real, int32_t* real_in_fake, float* real_min_d2, int32_t* real_min_j);
+
 /* ---- linear probe of the latent means on the device (csrc/probe.hip): one evaluation of the multinomial logistic
  * regression (softmax regression) loss and gradient over all rows -- the hot path of an L-BFGS fit -- and the scores of a fitted probe.  The
  * reference has none of it.  With u = 2^-24, Z [n][ldz] f32, classes int32 [n], W [D][ldw], b [C] (all device memory):
