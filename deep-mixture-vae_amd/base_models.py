@@ -631,6 +631,101 @@ class DeepMixtureVAE(VAE):
         res.update(n_real=N, n_samples=M, space=space)
         return res
 
+    def get_reconstruction_quality(self, session, data, image_shape=None, n_worst=10, window=None, data_range=1.0, return_images=False):
+        """How good are the reconstructions, and for which rows are they bad?  The structural similarity (Wang et al. 2004) of every row
+        of `data` with its reconstruction -- the decoder's mean image of the encoder's mean, epsilon = 0: the images reconstruct(X)
+        returns -- on the GPU (dmvae_hip.ssim, csrc/ssim.hip: valid windows, centred moments), beside the mean squared error.  Returns
+        dict(ssim, mse, psnr, n, image_shape, worst, worst_ssim) and, when `data` holds classes, ssim_per_class and mse_per_class (nan for a
+        class without rows).  ssim and mse are the means over the rows, psnr = 10 log10(data_range^2 / mse) of that mean mse (inf at 0);
+        worst: the n_worst rows of lowest SSIM in the data set's own numbering, lowest first, a tie going to the row evaluated earlier
+        (a stable sort); worst_ssim their values.  image_shape: (H, W) or (planes, H, W); None means (sqrt(input_dim), sqrt(input_dim)),
+        a ValueError when input_dim is no perfect square.  window: the 1-D weights of the separable window (default: Gaussian, 11 taps,
+        sigma 1.5).  Walks `data` in its current order WITHOUT reshuffling and draws nothing from the NumPy stream; writes no parameter,
+        moment or step state.  Per batch: gather, encode, decode the "mean" view, an f32 copy of "recon", one dmvae_ssim_rows launch that
+        reads the resident rows through the evaluated order.  The loop only enqueues; one f32 vector [ssim | sse] comes back at the end
+        and the group means are taken from it on the host in float64 (np.bincount: a device index_add_ would be a float atomic).
+        return_images: (the dict, the reconstructions f32 [n][input_dim] on the device, in the evaluated order) instead."""
+        import torch
+        from dmvae_hip import ssim as S
+        shape = S._plane_shape(S.default_image_shape(self.input_dim) if image_shape is None else image_shape, self.input_dim)
+        S._window(window, shape[1], shape[2])
+        eng, dev, N = self._engine, self._session.device, len(data.order)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        parts_s, parts_e, images = [], [], []
+        rows = data.device_rows(dev)
+        for s, n in self._eval_batches(data, data.order):
+            eng.encode(n)
+            Z = torch.empty((n, self.latent_dim), dtype=torch.float32, device=dev)
+            Z.copy_(eng.view("mean", n))
+            eng.decode(Z)
+            Y = torch.empty((n, self.input_dim), dtype=torch.float32, device=dev)
+            Y.copy_(eng.view("recon", n))                        # (casts a bf16 plan's view to f32)
+            sv, ev = S.ssim_enqueue(rows, Y, shape, ix=self._eval_perm[s:s + n], window=window, data_range=data_range, flag=flag)
+            parts_s.append(sv)
+            parts_e.append(ev)
+            if return_images:
+                images.append(Y)
+        host = torch.cat(parts_s + parts_e + [flag.view(torch.float32)]).cpu().numpy()
+        if int(host[2 * N:].view(np.int32)[0]):
+            raise IndexError("reconstruction quality on the device: a row index out of range")
+        sv, mse_rows, _ = S.quality_from(host[:N], host[N:2 * N], self.input_dim, data_range)
+        mse = float(mse_rows.mean())
+        idx = np.argsort(sv, kind="stable")[:max(0, int(n_worst))]
+        res = dict(ssim=float(sv.mean()), mse=mse, psnr=float("inf") if mse == 0.0 else float(10.0 * np.log10(float(data_range) ** 2 / mse)), n=N,
+                   image_shape=shape if image_shape is not None and len(tuple(image_shape)) == 3 else shape[1:],
+                   worst=np.asarray(data.order)[idx].astype(np.int64), worst_ssim=sv[idx])
+        cls = getattr(data, "_cls", None)
+        if cls is not None and np.issubdtype(np.asarray(cls).dtype, np.integer) and len(cls) == len(data.order):
+            g, G = np.asarray(cls)[data.order], int(np.max(cls)) + 1
+            count = np.bincount(g, minlength=G)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                res["ssim_per_class"] = np.bincount(g, weights=sv, minlength=G) / count
+                res["mse_per_class"] = np.bincount(g, weights=mse_rows, minlength=G) / count
+        return (res, torch.cat(images)) if return_images else res
+
+    def get_sample_diversity(self, session, n_per_cluster=32, image_shape=None, counter=0, collapsed_above=0.9, window=None, data_range=1.0):
+        """Has a mixture component collapsed onto one image, or do two components generate the same thing?  The mean pairwise SSIM among
+        decoded draws from the prior (Odena et al. 2017), per component, on the GPU (dmvae_hip.ssim.pairwise_enqueue).  The draws are
+        sample_prior_device(n_per_cluster K, counter): the samples get_sample_quality judges at the same counter, row j from component
+        j mod K.  Returns dict(ssim_within [K], ssim_between, ssim_between_per_cluster [K], collapsed, n_per_cluster, image_shape):
+        ssim_within[c] = the mean SSIM over all n_per_cluster (n_per_cluster - 1) / 2 pairs of component c's draws (1 = one image);
+        ssim_between = the mean over the pairs (draw t of c, draw t of c') for c < c' and all t, ssim_between_per_cluster[c] the mean over
+        those of them that involve c (nan for K = 1); collapsed = the components whose within-value exceeds collapsed_above -- 0.9 is a
+        convention, not a theorem: distinct MNIST digits of one class lie near 0.2 - 0.5.  Draws nothing from the NumPy stream and writes
+        no parameter, moment or step state.  Only enqueues; one f32 vector comes back at the end, the means are float64 on the host.
+        ValueError unless n_per_cluster >= 2."""
+        import torch
+        from dmvae_hip import ssim as S
+        shape = S._plane_shape(S.default_image_shape(self.input_dim) if image_shape is None else image_shape, self.input_dim)
+        S._window(window, shape[1], shape[2])
+        K, m, dev = self.n_classes, int(n_per_cluster), self._session.device
+        if m < 2:
+            raise ValueError("n_per_cluster = %d: a component needs two draws for a pair" % m)
+        X, _, _ = self.sample_prior_device(m * K, counter)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        comp = np.arange(m * K) % K
+        sw, _, _, _, _ = S.pairwise_enqueue(X, comp, K, shape, window=window, data_range=data_range, flag=flag)
+        parts = [sw]
+        if K > 1:
+            ca, cb = np.triu_indices(K, 1)                       # the pairs c < c', for every t: rows t K + c and t K + c'
+            base = (np.arange(m) * K)[:, None]
+            sb, _ = S.ssim_enqueue(X, X, shape, ix=(base + ca[None, :]).reshape(-1), iy=(base + cb[None, :]).reshape(-1), window=window,
+                                   data_range=data_range, flag=flag)
+            parts.append(sb)
+        host = torch.cat(parts + [flag.view(torch.float32)]).cpu().numpy()
+        if int(host[-1:].view(np.int32)[0]):
+            raise IndexError("sample diversity on the device: a row index out of range")
+        P = m * (m - 1) // 2
+        within = host[:K * P].astype(np.float64).reshape(K, P).mean(axis=1)
+        between, per = float("nan"), np.full(K, np.nan)
+        if K > 1:
+            vb = host[K * P:-1].astype(np.float64).reshape(m, len(ca))
+            between = float(vb.mean())
+            per = np.array([vb[:, (ca == c) | (cb == c)].mean() for c in range(K)])
+        return dict(ssim_within=within, ssim_between=between, ssim_between_per_cluster=per,
+                    collapsed=[int(c) for c in np.nonzero(within > float(collapsed_above))[0]], n_per_cluster=m,
+                    image_shape=shape if image_shape is not None and len(tuple(image_shape)) == 3 else shape[1:])
+
     # ------------------------------------------------------------------ pretraining (base_models.py:304-423)
     # the variables tf.get_collection(TRAINABLE_VARIABLES, scope=name + "/encoder_network/c") returns (:313-315)
     PRIOR_VAR_LIST = ("W_ch", "b_ch", "W_logits", "b_logits")

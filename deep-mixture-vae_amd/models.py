@@ -204,6 +204,15 @@ class MoE:
         """Precision, recall, density and coverage of the gate's decoded prior samples (DeepMixtureVAE.get_sample_quality).  No reshuffle."""
         return self.vae.get_sample_quality(session, data, k=k, n_samples=n_samples, space=space, counter=counter)
 
+    def get_reconstruction_quality(self, session, data, image_shape=None, n_worst=10, **kw):
+        """SSIM, PSNR and MSE of the gate's reconstructions, per class, with the worst rows (DeepMixtureVAE.get_reconstruction_quality).
+        No reshuffle."""
+        return self.vae.get_reconstruction_quality(session, data, image_shape=image_shape, n_worst=n_worst, **kw)
+
+    def get_sample_diversity(self, session, n_per_cluster=32, image_shape=None, counter=0, **kw):
+        """Mean pairwise SSIM among the gate's decoded prior samples, within and between components (DeepMixtureVAE.get_sample_diversity)."""
+        return self.vae.get_sample_diversity(session, n_per_cluster=n_per_cluster, image_shape=image_shape, counter=counter, **kw)
+
     def get_cluster_exemplars(self, session, data, n=10):
         """The rows of `data` nearest each expert's prior mean (DeepMixtureVAE.get_cluster_exemplars).  No reshuffle."""
         return self.vae.get_cluster_exemplars(session, data, n=n)

@@ -22,6 +22,9 @@ New flags (defaults = reference behaviour): --batch_size, --dtype, --seed,
 fitted on the train split's latent means, get_linear_probe_accuracy),
 --sample_quality K (per epoch on the test set: improved precision / recall and density / coverage of the decoded draws from the mixture prior,
 K-th-neighbour balls, per prior component and per class, get_sample_quality; 0 = off),
+--recon_quality (per epoch on the test set: SSIM, PSNR and MSE of the reconstructions, per class, get_reconstruction_quality),
+--sample_diversity N (per epoch: the mean pairwise SSIM among N decoded prior draws per mixture component, within and between components,
+get_sample_diversity; 0 = off),
 --tsne (off | host | device: with --plotting, sampled.png gains the t-SNE scatter of the prior samples, embedded by sklearn on the CPU or by
 the exact t-SNE in HIP, dmvae_hip.tsne.TSNE).
 """
@@ -119,6 +122,14 @@ parser.add_argument("--sample_quality", type=int, default=0,
                          "cover the test set: improved precision / recall and density / coverage with K-th-neighbour balls in the space of the "
                          "encoder means, per prior component and per class in the JSONL record, all pairs on the device (get_sample_quality); "
                          "rank 0 alone evaluates; 0 = off")
+parser.add_argument("--recon_quality", action="store_true", default=False,
+                    help="add ssimTest and psnrTest to the epoch line -- the structural similarity (valid 11-tap Gaussian windows, centred moments) "
+                         "and the PSNR of the test set's reconstructions -- and those, mseTest and the per-class vectors to the JSONL record, on "
+                         "the device (get_reconstruction_quality); rank 0 alone evaluates")
+parser.add_argument("--sample_diversity", type=int, default=0,
+                    help="N > 0 adds divTest to the epoch line -- the mean pairwise SSIM among N decoded prior draws of one mixture component, "
+                         "averaged over the components (near 1: a component generates one image) -- and the per-component vectors to the JSONL "
+                         "record, on the device (get_sample_diversity); rank 0 alone evaluates; 0 = off")
 parser.add_argument("--tsne", type=str, default="off", choices=["off", "host", "device"],
                     help="--plotting: add the t-SNE scatter of the prior samples (1000 per cluster) to sampled.png, embedded with sklearn on the "
                          "host (the reference's call) or with the exact t-SNE on the device (dmvae_hip.tsne.TSNE); off = the sample grid alone")
@@ -147,6 +158,22 @@ def _sample_quality_record(sq):
                density_per_cluster=vec(sq["density_per_cluster"]))
     if "coverage_per_class" in sq:
         rec.update(coverage_per_class=vec(sq["coverage_per_class"]), recall_per_class=vec(sq["recall_per_class"]))
+    return rec
+
+
+def _ssim_record(rq, sd):
+    """the JSONL keys of --recon_quality and --sample_diversity (nan, and the PSNR of an exact reconstruction, are written as null)"""
+    num = lambda x: float(x) if math.isfinite(x) else None
+    vec = lambda v: [num(x) for x in v]
+    rec = {}
+    if rq is not None:
+        rec.update(ssimTest=float(rq["ssim"]), psnrTest=num(rq["psnr"]), mseTest=float(rq["mse"]), worst_rows_test=[int(i) for i in rq["worst"]])
+        if "ssim_per_class" in rq:
+            rec.update(ssim_per_class=vec(rq["ssim_per_class"]), mse_per_class=vec(rq["mse_per_class"]))
+    if sd is not None:
+        rec.update(divTest=float(np.mean(sd["ssim_within"])), div_n=int(sd["n_per_cluster"]), ssim_within=vec(sd["ssim_within"]),
+                   ssim_between=num(sd["ssim_between"]), ssim_between_per_cluster=vec(sd["ssim_between_per_cluster"]),
+                   collapsed=list(sd["collapsed"]))
     return rec
 
 
@@ -272,6 +299,8 @@ def main(argv):
             knnTest = model.get_knn_accuracy(sess, knn_data, test_data, k=argv.knn) if knn_data is not None else None
             probeTest = model.get_linear_probe_accuracy(sess, probe_data, test_data, C=argv.probe_C) if probe_data is not None else None
             sqTest = model.get_sample_quality(sess, test_data, k=argv.sample_quality, counter=epoch) if argv.sample_quality > 0 and rank == 0 else None
+            rqTest = model.get_reconstruction_quality(sess, test_data) if argv.recon_quality and rank == 0 else None
+            sdTest = model.get_sample_diversity(sess, n_per_cluster=argv.sample_diversity, counter=epoch) if argv.sample_diversity > 0 and rank == 0 else None
             improved = accTest > maxAcc
             if world > 1:
                 # the branch below holds a COLLECTIVE (sync_master): rank 0 decides and every rank follows.  Each rank scores the same
@@ -310,6 +339,7 @@ def main(argv):
                     rec.update(probeTest=float(probeTest), probe_C=argv.probe_C, probe_iters=model.last_linear_probe_.n_iter_)
                 if sqTest is not None:
                     rec.update(_sample_quality_record(sqTest))
+                rec.update(_ssim_record(rqTest, sdTest))
                 with open(argv.model + "_metrics.jsonl", "a") as fl:
                     fl.write(json.dumps(rec) + "\n")
             if math.isnan(loss):
@@ -328,6 +358,10 @@ def main(argv):
                 postfix["probeTest"] = "%.4f" % probeTest
             if sqTest is not None:
                 postfix.update(precTest="%.4f" % sqTest["precision"], covTest="%.4f" % sqTest["coverage"])
+            if rqTest is not None:
+                postfix.update(ssimTest="%.4f" % rqTest["ssim"], psnrTest="%.2f" % rqTest["psnr"])
+            if sdTest is not None:
+                postfix["divTest"] = "%.4f" % float(np.mean(sdTest["ssim_within"]))
             bar.set_postfix(postfix)
     if plotting:                                                  # train.py:332-334
         visualization.mnist_sample_plot(model, sess, tsne=argv.tsne != "off", tsne_backend=argv.tsne if argv.tsne != "off" else "host")
@@ -395,6 +429,8 @@ def main_moe(argv, world, rank):
         knnTest = model.get_knn_accuracy(sess, train_data, test_data, k=argv.knn) if argv.knn > 0 else None
         probeTest = model.get_linear_probe_accuracy(sess, train_data, test_data, C=argv.probe_C) if argv.probe else None
         sqTest = model.get_sample_quality(sess, test_data, k=argv.sample_quality, counter=epoch) if argv.sample_quality > 0 else None
+        rqTest = model.get_reconstruction_quality(sess, test_data) if argv.recon_quality else None
+        sdTest = model.get_sample_diversity(sess, n_per_cluster=argv.sample_diversity, counter=epoch) if argv.sample_diversity > 0 else None
         if accTest > maxAcc:
             maxAcc = accTest
             with open(ckpt_path + ".tmp", "wb") as f:
@@ -412,6 +448,7 @@ def main_moe(argv, world, rank):
             rec.update(probeTest=float(probeTest), probe_C=argv.probe_C, probe_iters=model.last_linear_probe_.n_iter_)
         if sqTest is not None:
             rec.update(_sample_quality_record(sqTest))
+        rec.update(_ssim_record(rqTest, sdTest))
         with open(argv.model + "_metrics.jsonl", "a") as fl:
             fl.write(json.dumps(rec) + "\n")
         print(json.dumps(rec))

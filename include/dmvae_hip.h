@@ -764,6 +764,30 @@ int dmvae_knn_ranks(void* stream, const float* X, int64_t ldx, int N, int D, con
 int dmvae_prdc_counts(void* stream, const float* R, int64_t ldr, int N, const float* F, int64_t ldf, int M, int D, const float* rR2,
                       const float* rF2, int32_t* fake_in_real, int32_t* real_in_fake, float* real_min_d2, int32_t* real_min_j);
 
+/* ---- structural similarity on the device (csrc/ssim.hip): the SSIM of Wang et al. 2004 and the squared error of
+ * n_pairs comparisons of image rows.  The reference has none of it.  Comparison r reads row X[ix ? ix[r] : r] and row Y[iy ? iy[r] : r]
+ * (ix, iy: device int32 [n_pairs] or NULL; X and Y may be the same buffer).  A row is `planes` images of H x W f32, one after another; ldx,
+ * ldy >= planes H W are the row strides, and what lies between the rows is never read.  The window is separable: the 2-D weight is
+ * g[a][b] = fl32(w1[a] w1[b]); w1 is a HOST pointer to win floats, read at call time -- it travels in the kernel's argument struct and is not
+ * kept.  win is odd, 3 <= win <= 11, win <= min(H, W).  Only windows that lie wholly inside the image count (VALID): for win = 11 and a
+ * Gaussian of sigma 1.5 that is skimage's structural_similarity(gaussian_weights=True, use_sample_covariance=False), whose crop of
+ * (win - 1) / 2 pixels never sees the padding.  Per window, in f32 with every product and sum rounded where it is written:
+ *   mx = sum g x, my = sum g y                    acc = fmaf(g, x, acc), a ascending, b ascending inside it
+ *   sxx = sum g (x - mx)^2, syy, sxy alike        acc = fmaf(g, fl(dx dy), acc): CENTRED on the window's own means; no E[x^2] - mu^2 anywhere
+ *   S = (2 fl(mx my) + c1) (2 sxy + c2) / ((fl(mx mx) + fl(my my) + c1) (sxx + syy + c2))      the division correctly rounded
+ * ssim[r] (device f32 [n_pairs]) = the mean of S over all windows of all planes (summed in f64, a fixed order); sse[r] (device f32
+ * [n_pairs], may be NULL) = sum (x - y)^2 over the whole row -- a SUM, callers divide -- exact on rows of multiples of 1/16.  Two
+ * properties hold in BITS because the sequence is pinned: ssim(X, X) == 1.0f, and ssim(X, Y) == ssim(Y, X).  There are no atomics on
+ * floats; a wave owns a comparison and sums in a fixed order, so two calls return the same bits.  An ix / iy entry outside [0, nx) /
+ * [0, ny) reads nothing: NaN goes to that comparison's outputs and bit 1 of *err_flag (device int32, OR-ed into, may be NULL) is set.
+ * One launch, no memset; the call only enqueues and never synchronises; every argument is checked before anything is enqueued, with the
+ * entry's name in the error text.  DMVAE_EINVAL: a null X / Y / ssim / w1; n_pairs, nx, ny, H, W or planes < 1; win even, outside 3 .. 11
+ * or above min(H, W); ldx or ldy below planes H W.  DMVAE_EUNSUPPORTED: H W > 4096 (the two planes of a pair are held in 32 KiB of LDS).
+ * Rows are indexed in 64 bits. */
+int dmvae_ssim_rows(void* stream, const float* X, int64_t ldx, int64_t nx, const int32_t* ix, const float* Y, int64_t ldy, int64_t ny,
+                    const int32_t* iy, int64_t n_pairs, int H, int W, int planes, const float* w1, int win, float c1, float c2, float* ssim,
+                    float* sse, int32_t* err_flag);
+
 /* ---- linear probe of the latent means on the device (csrc/probe.hip): one evaluation of the multinomial logistic
  * regression (softmax regression) loss and gradient over all rows -- the hot path of an L-BFGS fit -- and the scores of a fitted probe.  The
  * reference has none of it.  With u = 2^-24, Z [n][ldz] f32, classes int32 [n], W [D][ldw], b [C] (all device memory):
