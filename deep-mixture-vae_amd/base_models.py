@@ -585,28 +585,12 @@ class DeepMixtureVAE(VAE):
             X[s:s + b].copy_(eng.view("recon", b))               # (casts a bf16 plan's view to f32)
         return X, Z, comp.to(torch.int32)
 
-    def get_sample_quality(self, session, data, k=5, n_samples=None, space="latent", counter=0):
-        """Are the decoded draws from the mixture prior p(z) = 1/K sum_c N(mu_c, diag exp(lv_c)) realistic, and do they cover the data?
-        Improved precision and recall (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020) of M generated rows
-        against the N rows of `data`, all pairs on the GPU (dmvae_hip.prdc, csrc/prdc.hip), k-th-neighbour balls closed, squared radii
-        from dmvae_knn.  Returns dict(precision, recall, density, coverage, k, n_real, n_samples, space,
-        precision_per_cluster [K], density_per_cluster [K]) -- which component generates junk -- and, when `data` holds classes,
-        coverage_per_class and recall_per_class -- which classes the prior misses (nan for a class without rows).
-        Generated rows: M = n_samples, by default N rounded down to a multiple of K; row j comes from component j mod K (the uniform
-        prior of the KL_C term), z = mu_c + exp(lv_c / 2) eps with eps from the device's Philox stream 7 keyed by (seed, counter),
-        decoded in batches.  A generated row is the decoder's MEAN image (the "recon" view), not a Bernoulli draw from it.
-        space="latent" (default): features are encoder means -- of the real rows, and of the generated rows encoded again;
-        space="input": the rows themselves, D = input_dim.  Walks `data` in its current order WITHOUT reshuffling and draws nothing
-        from the NumPy stream; writes no parameter, moment or step state.  The loop only enqueues; one copy comes back at the end.
-        ValueError unless 1 <= k <= min(256, N - 1, M - 1) and space is one of the two."""
+    def _real_and_generated_features(self, data, M, space, counter):
+        """what get_sample_quality and get_sample_distance compare: (R f32 [N][D] of the rows of `data` in their current order, F f32 [M][D]
+        of the M rows of sample_prior_device(M, counter), the component of every generated row, the class of every real row -- or None -- and
+        the number of classes).  space="latent": encoder means on both sides; "input": the rows themselves.  Only enqueues."""
         import torch
-        from dmvae_hip import prdc
-        if space not in ("latent", "input"):
-            raise ValueError("space = %r: 'latent' or 'input'" % (space,))
-        eng, dev, K, N = self._engine, self._session.device, self.n_classes, len(data.order)
-        M = (N // K) * K if n_samples is None else int(n_samples)
-        if not 1 <= int(k) <= min(256, N - 1, M - 1):
-            raise ValueError("k = %d: 1 <= k <= min(256, the %d real rows - 1, the %d generated rows - 1)" % (k, N, M))
+        eng, dev = self._engine, self._session.device
         X, _, comp = self.sample_prior_device(M, counter)
         if space == "latent":
             F = torch.empty((M, self.latent_dim), dtype=torch.float32, device=dev)
@@ -623,12 +607,68 @@ class DeepMixtureVAE(VAE):
         real_groups = n_groups = None
         if cls is not None and np.issubdtype(np.asarray(cls).dtype, np.integer) and len(cls) == len(data.order):
             real_groups, n_groups = data.device_classes(dev)[self._eval_perm.long()], int(np.max(cls)) + 1
+        return R, F, comp, real_groups, n_groups
+
+    def get_sample_quality(self, session, data, k=5, n_samples=None, space="latent", counter=0):
+        """Are the decoded draws from the mixture prior p(z) = 1/K sum_c N(mu_c, diag exp(lv_c)) realistic, and do they cover the data?
+        Improved precision and recall (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020) of M generated rows
+        against the N rows of `data`, all pairs on the GPU (dmvae_hip.prdc, csrc/prdc.hip), k-th-neighbour balls closed, squared radii
+        from dmvae_knn.  Returns dict(precision, recall, density, coverage, k, n_real, n_samples, space,
+        precision_per_cluster [K], density_per_cluster [K]) -- which component generates junk -- and, when `data` holds classes,
+        coverage_per_class and recall_per_class -- which classes the prior misses (nan for a class without rows).
+        Generated rows: M = n_samples, by default N rounded down to a multiple of K; row j comes from component j mod K (the uniform
+        prior of the KL_C term), z = mu_c + exp(lv_c / 2) eps with eps from the device's Philox stream 7 keyed by (seed, counter),
+        decoded in batches.  A generated row is the decoder's MEAN image (the "recon" view), not a Bernoulli draw from it.
+        space="latent" (default): features are encoder means -- of the real rows, and of the generated rows encoded again;
+        space="input": the rows themselves, D = input_dim.  Walks `data` in its current order WITHOUT reshuffling and draws nothing
+        from the NumPy stream; writes no parameter, moment or step state.  The loop only enqueues; one copy comes back at the end.
+        ValueError unless 1 <= k <= min(256, N - 1, M - 1) and space is one of the two."""
+        from dmvae_hip import prdc
+        if space not in ("latent", "input"):
+            raise ValueError("space = %r: 'latent' or 'input'" % (space,))
+        K, N = self.n_classes, len(data.order)
+        M = (N // K) * K if n_samples is None else int(n_samples)
+        if not 1 <= int(k) <= min(256, N - 1, M - 1):
+            raise ValueError("k = %d: 1 <= k <= min(256, the %d real rows - 1, the %d generated rows - 1)" % (k, N, M))
+        R, F, comp, real_groups, n_groups = self._real_and_generated_features(data, M, space, counter)
         flat, layout = prdc.prdc_enqueue(R, F, int(k), real_groups, comp, n_groups, K)
         res = prdc.prdc_from(flat, layout, N, M, int(k))
         res["precision_per_cluster"], res["density_per_cluster"] = np.array(res.pop("precision_per_group")), np.array(res.pop("density_per_group"))
         if real_groups is not None:
             res["coverage_per_class"], res["recall_per_class"] = np.array(res.pop("coverage_per_group")), np.array(res.pop("recall_per_group"))
         res.update(n_real=N, n_samples=M, space=space)
+        return res
+
+    def get_sample_distance(self, session, data, eps_rel=0.05, n_samples=None, space="latent", counter=0, tol=1e-4, max_iter=500):
+        """How far is the distribution of the decoded draws from the mixture prior from the distribution of the data?  The Sinkhorn
+        divergence S_eps (Feydy et al. 2019; debiased entropic optimal transport, cost = squared Euclidean distance, no 1/2: S_eps -> W_2^2
+        as eps -> 0) between M generated rows and the N rows of `data`, both uniformly weighted, on the GPU (dmvae_hip.sinkhorn,
+        csrc/sinkhorn.hip): 0 when the two coincide, in squared-distance units of the chosen space, no assumption on the clouds' shape.
+        eps = eps_rel x the mean squared distance over all pairs.  Returns dict(divergence, ot, eps, n_iter, err, n_real, n_samples, space,
+        per_cluster [K], mean_per_cluster [K]) -- the share of the divergence carried by the rows of each prior component and that share per
+        unit of mass: which component generates far from the data -- and, when `data` holds classes, per_class and mean_per_class -- which
+        classes are far from anything the prior generates (a class without rows: 0 and nan).  per_cluster and per_class together add up to
+        the divergence; a single entry may be negative.  n_iter and err: iterations (annealing included) and final marginal residual of the
+        three transport problems (data against samples, data against itself, samples against themselves).
+        The two row sets are those of get_sample_quality at the same arguments: M = n_samples, by default N rounded down to a multiple of K,
+        row j from component j mod K, z = mu_c + exp(lv_c / 2) eps with eps from the device's Philox stream 7 keyed by (seed, counter), the
+        decoder's MEAN image; space="latent" (default): encoder means of both sets, space="input": the rows themselves.  Walks `data` in its
+        current order WITHOUT reshuffling and draws nothing from the NumPy stream; writes no parameter, moment or step state.
+        ValueError unless space is one of the two, M >= 1, eps_rel > 0, tol >= 0 and max_iter >= 1."""
+        from dmvae_hip import sinkhorn
+        if space not in ("latent", "input"):
+            raise ValueError("space = %r: 'latent' or 'input'" % (space,))
+        K, N = self.n_classes, len(data.order)
+        M = (N // K) * K if n_samples is None else int(n_samples)
+        if M < 1 or not float(eps_rel) > 0 or not tol >= 0 or int(max_iter) < 1:
+            raise ValueError("n_samples = %d, eps_rel = %r, tol = %r, max_iter = %r: M >= 1, eps_rel > 0, tol >= 0, max_iter >= 1" % (M, eps_rel, tol, max_iter))
+        R, F, comp, real_groups, n_groups = self._real_and_generated_features(data, M, space, counter)
+        sd = sinkhorn.sinkhorn_divergence(R, F, eps_rel=eps_rel, tol=tol, max_iter=max_iter, real_groups=real_groups, fake_groups=comp,
+                                          n_real_groups=n_groups, n_fake_groups=K)
+        res = dict(divergence=sd["divergence"], ot=sd["ot"], eps=sd["eps"], n_iter=sd["n_iter"], err=sd["err"], n_real=N, n_samples=M, space=space,
+                   per_cluster=np.array(sd["per_fake_group"]), mean_per_cluster=np.array(sd["mean_per_fake_group"]))
+        if real_groups is not None:
+            res.update(per_class=np.array(sd["per_real_group"]), mean_per_class=np.array(sd["mean_per_real_group"]))
         return res
 
     def get_reconstruction_quality(self, session, data, image_shape=None, n_worst=10, window=None, data_range=1.0, return_images=False):

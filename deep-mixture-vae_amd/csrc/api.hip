@@ -20,6 +20,7 @@
 #include "mixture_density.h"
 #include "knn.h"
 #include "prdc.h"
+#include "sinkhorn.h"
 #include "ssim.h"
 #include "probe.h"
 #include "measure.h"
@@ -272,6 +273,10 @@ extern "C" int dmvae_knn_ranks(void* stream, const float* X, int64_t ldx, int N,
 extern "C" int dmvae_prdc_counts(void* stream, const float* R, int64_t ldr, int N, const float* F, int64_t ldf, int M, int D, const float* rR2,
                                  const float* rF2, int32_t* fake_in_real, int32_t* real_in_fake, float* real_min_d2, int32_t* real_min_j) {
     return prdc_counts_launch((hipStream_t)stream, R, ldr, N, F, ldf, M, D, rR2, rF2, fake_in_real, real_in_fake, real_min_d2, real_min_j);
+}
+extern "C" int dmvae_sinkhorn_softmin(void* stream, const float* X, int64_t ldx, int N, const float* Y, int64_t ldy, int M, int D, const float* g,
+                                      const float* log_b, float eps, const float* prev, float* out) {
+    return sinkhorn_softmin_launch((hipStream_t)stream, X, ldx, N, Y, ldy, M, D, g, log_b, eps, prev, out);
 }
 extern "C" int dmvae_ssim_rows(void* stream, const float* X, int64_t ldx, int64_t nx, const int32_t* ix, const float* Y, int64_t ldy, int64_t ny,
                                const int32_t* iy, int64_t n_pairs, int H, int W, int planes, const float* w1, int win, float c1, float c2, float* ssim,

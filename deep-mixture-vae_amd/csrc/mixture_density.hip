@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "mixture_density.h"
+#include "lse.h"                                 // MdLse, md_join: the running logsumexp pair
 
 namespace dmvae {
 
@@ -63,18 +64,6 @@ __global__ __launch_bounds__(256) void md_pad_kernel(const float* __restrict__ Z
     if (idx >= (int64_t)Mp * Dp) return;
     const int i = (int)(idx / Dp), d = (int)(idx % Dp);
     zp[idx] = (i < M && d < D) ? Z[(int64_t)i * ldz + d] : 0.f;
-}
-
-// a running logsumexp: sum = s * exp(m); the empty pair is (-inf, 0)
-struct MdLse { float m; double s; };
-
-__device__ __forceinline__ MdLse md_join(MdLse a, MdLse b) {
-#pragma clang fp contract(off)                   // (a, b) and (b, a) give the same bits: both lanes of a butterfly step hold one value
-    const float M = fmaxf(a.m, b.m);
-    const bool some = M > -INFINITY;
-    const double ea = (double)__expf(some ? a.m - M : 0.f), eb = (double)__expf(some ? b.m - M : 0.f);
-    const double pa = a.s * ea, pb = b.s * eb;
-    return MdLse{M, pa + pb};
 }
 
 __device__ __forceinline__ float md_finish(MdLse v, double add) {

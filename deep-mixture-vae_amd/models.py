@@ -204,6 +204,11 @@ class MoE:
         """Precision, recall, density and coverage of the gate's decoded prior samples (DeepMixtureVAE.get_sample_quality).  No reshuffle."""
         return self.vae.get_sample_quality(session, data, k=k, n_samples=n_samples, space=space, counter=counter)
 
+    def get_sample_distance(self, session, data, eps_rel=0.05, n_samples=None, space="latent", counter=0, tol=1e-4, max_iter=500):
+        """Sinkhorn divergence between the gate's decoded prior samples and the data (DeepMixtureVAE.get_sample_distance).  No reshuffle."""
+        return self.vae.get_sample_distance(session, data, eps_rel=eps_rel, n_samples=n_samples, space=space, counter=counter, tol=tol,
+                                            max_iter=max_iter)
+
     def get_reconstruction_quality(self, session, data, image_shape=None, n_worst=10, **kw):
         """SSIM, PSNR and MSE of the gate's reconstructions, per class, with the worst rows (DeepMixtureVAE.get_reconstruction_quality).
         No reshuffle."""

@@ -22,6 +22,8 @@ New flags (defaults = reference behaviour): --batch_size, --dtype, --seed,
 fitted on the train split's latent means, get_linear_probe_accuracy),
 --sample_quality K (per epoch on the test set: improved precision / recall and density / coverage of the decoded draws from the mixture prior,
 K-th-neighbour balls, per prior component and per class, get_sample_quality; 0 = off),
+--sample_distance (per epoch on the test set: the Sinkhorn divergence between the decoded draws from the mixture prior and the data, per prior
+component and per class, get_sample_distance),
 --recon_quality (per epoch on the test set: SSIM, PSNR and MSE of the reconstructions, per class, get_reconstruction_quality),
 --sample_diversity N (per epoch: the mean pairwise SSIM among N decoded prior draws per mixture component, within and between components,
 get_sample_diversity; 0 = off),
@@ -122,6 +124,11 @@ parser.add_argument("--sample_quality", type=int, default=0,
                          "cover the test set: improved precision / recall and density / coverage with K-th-neighbour balls in the space of the "
                          "encoder means, per prior component and per class in the JSONL record, all pairs on the device (get_sample_quality); "
                          "rank 0 alone evaluates; 0 = off")
+parser.add_argument("--sample_distance", action="store_true", default=False,
+                    help="add sdTest to the epoch line -- how far the distribution of the decoded draws from the mixture prior is from the test "
+                         "set's: the Sinkhorn divergence (debiased entropic optimal transport, squared Euclidean cost) between their encoder "
+                         "means, with its split per prior component and per class in the JSONL record, all pairs on the device "
+                         "(get_sample_distance); rank 0 alone evaluates")
 parser.add_argument("--recon_quality", action="store_true", default=False,
                     help="add ssimTest and psnrTest to the epoch line -- the structural similarity (valid 11-tap Gaussian windows, centred moments) "
                          "and the PSNR of the test set's reconstructions -- and those, mseTest and the per-class vectors to the JSONL record, on "
@@ -158,6 +165,15 @@ def _sample_quality_record(sq):
                density_per_cluster=vec(sq["density_per_cluster"]))
     if "coverage_per_class" in sq:
         rec.update(coverage_per_class=vec(sq["coverage_per_class"]), recall_per_class=vec(sq["recall_per_class"]))
+    return rec
+
+
+def _sample_distance_record(sk):
+    """the JSONL keys of --sample_distance (a class without rows is written as null in its mean; the means stay out of the record)"""
+    rec = dict(sdTest=float(sk["divergence"]), sd_eps=float(sk["eps"]), sd_iters=[int(n) for n in sk["n_iter"]], sd_err=[float(e) for e in sk["err"]],
+               sd_per_cluster=[float(x) for x in sk["per_cluster"]])
+    if "per_class" in sk:
+        rec.update(sd_per_class=[float(x) for x in sk["per_class"]])
     return rec
 
 
@@ -299,6 +315,7 @@ def main(argv):
             knnTest = model.get_knn_accuracy(sess, knn_data, test_data, k=argv.knn) if knn_data is not None else None
             probeTest = model.get_linear_probe_accuracy(sess, probe_data, test_data, C=argv.probe_C) if probe_data is not None else None
             sqTest = model.get_sample_quality(sess, test_data, k=argv.sample_quality, counter=epoch) if argv.sample_quality > 0 and rank == 0 else None
+            skTest = model.get_sample_distance(sess, test_data, counter=epoch) if argv.sample_distance and rank == 0 else None
             rqTest = model.get_reconstruction_quality(sess, test_data) if argv.recon_quality and rank == 0 else None
             sdTest = model.get_sample_diversity(sess, n_per_cluster=argv.sample_diversity, counter=epoch) if argv.sample_diversity > 0 and rank == 0 else None
             improved = accTest > maxAcc
@@ -339,6 +356,8 @@ def main(argv):
                     rec.update(probeTest=float(probeTest), probe_C=argv.probe_C, probe_iters=model.last_linear_probe_.n_iter_)
                 if sqTest is not None:
                     rec.update(_sample_quality_record(sqTest))
+                if skTest is not None:
+                    rec.update(_sample_distance_record(skTest))
                 rec.update(_ssim_record(rqTest, sdTest))
                 with open(argv.model + "_metrics.jsonl", "a") as fl:
                     fl.write(json.dumps(rec) + "\n")
@@ -358,6 +377,8 @@ def main(argv):
                 postfix["probeTest"] = "%.4f" % probeTest
             if sqTest is not None:
                 postfix.update(precTest="%.4f" % sqTest["precision"], covTest="%.4f" % sqTest["coverage"])
+            if skTest is not None:
+                postfix["sdTest"] = "%.4f" % skTest["divergence"]
             if rqTest is not None:
                 postfix.update(ssimTest="%.4f" % rqTest["ssim"], psnrTest="%.2f" % rqTest["psnr"])
             if sdTest is not None:
@@ -429,6 +450,7 @@ def main_moe(argv, world, rank):
         knnTest = model.get_knn_accuracy(sess, train_data, test_data, k=argv.knn) if argv.knn > 0 else None
         probeTest = model.get_linear_probe_accuracy(sess, train_data, test_data, C=argv.probe_C) if argv.probe else None
         sqTest = model.get_sample_quality(sess, test_data, k=argv.sample_quality, counter=epoch) if argv.sample_quality > 0 else None
+        skTest = model.get_sample_distance(sess, test_data, counter=epoch) if argv.sample_distance else None
         rqTest = model.get_reconstruction_quality(sess, test_data) if argv.recon_quality else None
         sdTest = model.get_sample_diversity(sess, n_per_cluster=argv.sample_diversity, counter=epoch) if argv.sample_diversity > 0 else None
         if accTest > maxAcc:
@@ -448,6 +470,8 @@ def main_moe(argv, world, rank):
             rec.update(probeTest=float(probeTest), probe_C=argv.probe_C, probe_iters=model.last_linear_probe_.n_iter_)
         if sqTest is not None:
             rec.update(_sample_quality_record(sqTest))
+        if skTest is not None:
+            rec.update(_sample_distance_record(skTest))
         rec.update(_ssim_record(rqTest, sdTest))
         with open(argv.model + "_metrics.jsonl", "a") as fl:
             fl.write(json.dumps(rec) + "\n")

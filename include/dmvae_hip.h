@@ -764,6 +764,28 @@ int dmvae_knn_ranks(void* stream, const float* X, int64_t ldx, int N, int D, con
 int dmvae_prdc_counts(void* stream, const float* R, int64_t ldr, int N, const float* F, int64_t ldf, int M, int D, const float* rR2,
                       const float* rF2, int32_t* fake_in_real, int32_t* real_in_fake, float* real_min_d2, int32_t* real_min_j);
 
+/* ---- Sinkhorn divergence on the device (csrc/sinkhorn.hip): the softmin pass of the log-domain Sinkhorn iteration
+ * behind the debiased entropic optimal-transport cost S_eps (Feydy et al. 2019; Genevay et al. 2018) between decoded prior draws and data.
+ * The reference has none of it.  X [N][ldx] and Y [M][ldy] are f32 rows (unit column stride, D columns used; what lies between the rows is
+ * not read).  The cost is C_ij = d2(X_i, Y_j), THE distance of dmvae_knn above -- acc = fmaf(x_c - y_c, x_c - y_c, acc), f32 differences, c
+ * ascending, acc starting at 0 -- from the same tile body, so a pair's bits are those dmvae_knn returns.  No 1/2 factor: as eps -> 0,
+ * S_eps -> the squared 2-Wasserstein distance.  With g (device f32 [M], NULL: zeros) the column potentials, log_b (device f32 [M], NULL:
+ * -log M, the uniform weights; -inf: the column carries no mass) the column log-weights and eps > 0, all in f32 with 1 / eps rounded once:
+ *   h_j  = fmaf(g_j, 1 / eps, log_b_j)        t_ij = fmaf(-d2_ij, 1 / eps, h_j)        out_i = -eps logsumexp_j t_ij      (device f32 [N])
+ * the logsumexp as a running (maximum f32, scaled sum f64) with one f32 exponential per pair, -eps (m + log s) formed in double and rounded
+ * once.  With prev (device f32 [N]) non-NULL the entry writes (prev_i + out_i) / 2 instead -- formed in double, rounded once: the averaged
+ * update of the symmetric problems OT_eps(a, a).  A column with h_j = -inf never enters; a row whose columns are all empty gets +inf; no NaN
+ * is formed from finite inputs, whatever the size of g / eps.  The solver (dmvae_hip.sinkhorn) alternates f <- softmin_Y(g), g <- softmin_X(f)
+ * -- both this entry with the roles of X and Y swapped -- under an eps-scaling schedule; at a fixed point OT_eps = <a, f> + <b, g> and
+ *   S_eps = sum_i a_i (f_i - p_i) + sum_j b_j (g_j - q_j),      p and q the potentials of the symmetric problems of a and b.
+ * There are no float atomics: a workgroup owns 16 rows, walks every column, and joins its 256 partials per row in a fixed order, so two
+ * calls on the same inputs return the same bits.  One launch of ceil(N / 16) workgroups, no workspace, no memset -- both sets hold thousands
+ * of rows in every use; a small N is not split.  The call only enqueues and never synchronises; every argument is checked before anything is
+ * enqueued (DMVAE_EINVAL with the entry's name in the error text: N or M outside 1 .. 2^20, D < 1, ldx < D, ldy < D, eps not finite, not
+ * > 0 or so small that 1 / eps overflows f32, a null X / Y / out); rows are indexed in 64 bits. */
+int dmvae_sinkhorn_softmin(void* stream, const float* X, int64_t ldx, int N, const float* Y, int64_t ldy, int M, int D, const float* g,
+                           const float* log_b, float eps, const float* prev, float* out);
+
 /* ---- structural similarity on the device (csrc/ssim.hip): the SSIM of Wang et al. 2004 and the squared error of
  * n_pairs comparisons of image rows.  The reference has none of it.  Comparison r reads row X[ix ? ix[r] : r] and row Y[iy ? iy[r] : r]
  * (ix, iy: device int32 [n_pairs] or NULL; X and Y may be the same buffer).  A row is `planes` images of H x W f32, one after another; ldx,
