@@ -409,7 +409,7 @@ class DeepMixtureVAE(VAE):
         order = data.reshuffle()               # the reference iterates data.get_batches(), which reshuffles
         if self.eval == "device":
             return accuracy_from_confusion(self._device_confusion(data, order, self.n_classes), len(order))
-        _, _, logits = self.encode(data._rows[order])
+        _, _, logits = self.encode(data.data)   # (the rows in `order`: a binarised data set presents its current draw)
         return get_clustering_accuracy(logits, data._cls[order])
 
     def get_log_likelihood(self, session, data, k=50, counter=0):

@@ -21,6 +21,7 @@
 #include "knn.h"
 #include "prdc.h"
 #include "sinkhorn.h"
+#include "binarize.h"
 #include "ssim.h"
 #include "probe.h"
 #include "measure.h"
@@ -277,6 +278,10 @@ extern "C" int dmvae_prdc_counts(void* stream, const float* R, int64_t ldr, int 
 extern "C" int dmvae_sinkhorn_softmin(void* stream, const float* X, int64_t ldx, int N, const float* Y, int64_t ldy, int M, int D, const float* g,
                                       const float* log_b, float eps, const float* prev, float* out) {
     return sinkhorn_softmin_launch((hipStream_t)stream, X, ldx, N, Y, ldy, M, D, g, log_b, eps, prev, out);
+}
+extern "C" int dmvae_binarize_rows(void* stream, const float* X, int64_t ldx, int64_t n_rows, int n_cols, int64_t row_base, uint64_t seed, uint64_t counter,
+                                   int mode, float* out, int64_t ldo) {
+    return binarize_rows_launch((hipStream_t)stream, X, ldx, n_rows, n_cols, row_base, seed, counter, mode, out, ldo);
 }
 extern "C" int dmvae_ssim_rows(void* stream, const float* X, int64_t ldx, int64_t nx, const int32_t* ix, const float* Y, int64_t ldy, int64_t ny,
                                const int32_t* iy, int64_t n_pairs, int H, int W, int planes, const float* w1, int win, float c1, float c2, float* ssim,

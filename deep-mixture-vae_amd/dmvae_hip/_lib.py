@@ -49,6 +49,7 @@ EXPORTS = [
     "dmvae_knn_ws_bytes", "dmvae_knn", "dmvae_knn_vote", "dmvae_knn_ranks",
     "dmvae_prdc_counts",
     "dmvae_sinkhorn_softmin",
+    "dmvae_binarize_rows",
     "dmvae_ssim_rows",
     "dmvae_softmax_xent_ws_bytes", "dmvae_softmax_xent", "dmvae_linear_scores",
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
@@ -293,6 +294,7 @@ def _load():
         "dmvae_knn_ranks": [vp, vp, i64, i32, i32, vp, i64, i32, vp, i64, vp],
         "dmvae_prdc_counts": [vp, vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp],
         "dmvae_sinkhorn_softmin": [vp, vp, i64, i32, vp, i64, i32, i32, vp, vp, f32, vp, vp],
+        "dmvae_binarize_rows": [vp, vp, i64, i64, i32, i64, u64, u64, i32, vp, i64],
         "dmvae_ssim_rows": [vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, i32, i32, i32, vp, i32, f32, f32, vp, vp, vp],
         "dmvae_softmax_xent_ws_bytes": [i64, i32, i32],
         "dmvae_softmax_xent": [vp, vp, i64, i64, i32, vp, vp, vp, i32, vp, i64, vp, vp, i64, vp, vp],

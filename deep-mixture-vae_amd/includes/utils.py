@@ -146,16 +146,26 @@ def _device_classes(ds, device):
     return ds._device[key]
 
 
+BINARIZE_MODES = ("off", "static", "dynamic", "threshold")
+
+
 class Dataset:
     """includes/utils.py:428-466.  Same contract: shuffle on construction and at
     every get_batches() with the global NumPy RNG, consecutive batches, short
     last batch.  Instead of physically permuting the rows each epoch the class
     keeps the cumulative row order; `data` / `classes` present the permuted
     view, and the device-resident copy is gathered by that order on the GPU
-    (dmvae_gather_rows)."""
+    (dmvae_gather_rows).
 
-    def __init__(self, data, batch_size=100, shuffle=True):
+    binarize ("off" = the reference, grey levels as soft targets): "static" one Bernoulli draw of the rows, "dynamic" a
+    fresh draw per epoch -- the draw counter is the number of reshuffle() calls so far --, "threshold" x > 0.5.  The draw is made on the
+    device (dmvae_hip.binarize) into a second resident buffer that device_rows returns in place of the grey rows; binarize_seed keys it, and
+    the ranks of a data-parallel run pass the same one: they hold the whole data set and must agree on it.  No NumPy draw is consumed."""
+
+    def __init__(self, data, batch_size=100, shuffle=True, binarize="off", binarize_seed=0):
         data, classes = data
+        if binarize not in BINARIZE_MODES:
+            raise ValueError("binarize = %r: one of %s" % (binarize, ", ".join(BINARIZE_MODES)))
         self._rows = np.ascontiguousarray(np.asarray(data, dtype=np.float32))
         self._cls = np.copy(classes)
         self.order = np.arange(len(self._rows))
@@ -164,12 +174,17 @@ class Dataset:
         self.data_dim = self._rows.shape[1]
         self.epoch_len = int(math.ceil(len(self._rows) / batch_size))
         self._device = {}
+        self.binarize = binarize
+        self.binarize_seed = int(binarize_seed)
+        self._reshuffles = 0                   # reshuffle() calls so far: the draw counter of "dynamic"
+        self._draws = {}                       # device -> the counter of the draw its binarised buffer holds
+        self._host_draw = None                 # (counter, rows): the current draw, read back once
         if shuffle:
             self.order = self.order[np.random.permutation(len(self._rows))]
 
     @property
     def data(self):
-        return self._rows[self.order]
+        return self._host_rows()[self.order]
 
     @property
     def classes(self):
@@ -177,22 +192,56 @@ class Dataset:
 
     def reshuffle(self):
         """the per-epoch shuffle of get_batches (utils.py:450-454); returns the new row order"""
+        self._reshuffles += 1
         if self.shuffle:
             self.order = self.order[np.random.permutation(len(self._rows))]
         return self.order
 
     def get_batches(self):
         order = self.reshuffle()
+        rows = self._host_rows()
         for s in range(0, len(order), self.batch_size):
-            yield self._rows[order[s:s + self.batch_size]]
+            yield rows[order[s:s + self.batch_size]]
 
     def device_rows(self, device):
-        """the unpermuted rows, resident in HBM (uploaded once)"""
+        """the unpermuted rows, resident in HBM (uploaded once); binarised: the current draw of them, in a second buffer whose address never
+        changes (redrawn in place, on the current stream, when its draw counter is stale)"""
         import torch
         key = str(device)
         if key not in self._device:
             self._device[key] = torch.as_tensor(self._rows).to(device)
-        return self._device[key]
+        if self.binarize == "off":
+            return self._device[key]
+        return self._binarized_rows(device)
+
+    def draw_counter(self):
+        """the Philox counter of the current draw: reshuffle() calls so far under "dynamic", 0 otherwise"""
+        return self._reshuffles if self.binarize == "dynamic" else 0
+
+    def _binarized_rows(self, device):
+        import torch
+        from dmvae_hip.binarize import binarize
+        key = str(device)
+        if key not in self._draws:
+            self._device["binarized:" + key] = torch.empty_like(self._device[key])
+        out, counter = self._device["binarized:" + key], self.draw_counter()
+        if self._draws.get(key, (None, None))[1] != counter:
+            binarize(self._device[key], seed=self.binarize_seed, counter=counter, mode="threshold" if self.binarize == "threshold" else "bernoulli", out=out)
+            self._draws[key] = (device, counter)
+        return out
+
+    def _host_rows(self):
+        """the rows the host views present: the grey rows, or the current draw read back from the device (once per draw)"""
+        if self.binarize == "off":
+            return self._rows
+        counter = self.draw_counter()
+        if self._host_draw is None or self._host_draw[0] != counter:
+            if not self._draws:
+                raise RuntimeError("Dataset(binarize=%r): no device draw exists yet -- the rows are binarised by the HIP kernel on the device (there "
+                                   "is no CPU fallback); call device_rows(device) first" % self.binarize)
+            device = next(iter(self._draws.values()))[0]
+            self._host_draw = (counter, self.device_rows(device).cpu().numpy())
+        return self._host_draw[1]
 
     def device_classes(self, device):
         return _device_classes(self, device)

@@ -28,7 +28,11 @@ component and per class, get_sample_distance),
 --sample_diversity N (per epoch: the mean pairwise SSIM among N decoded prior draws per mixture component, within and between components,
 get_sample_diversity; 0 = off),
 --tsne (off | host | device: with --plotting, sampled.png gains the t-SNE scatter of the prior samples, embedded by sklearn on the CPU or by
-the exact t-SNE in HIP, dmvae_hip.tsne.TSNE).
+the exact t-SNE in HIP, dmvae_hip.tsne.TSNE),
+--binarize (off | static | dynamic | threshold; dmvae / vade: train and evaluate on binarised pixels, drawn on the device -- static: one Bernoulli
+draw of every row; dynamic: a fresh draw of the train set per epoch, the test set and the --knn / --probe split static; threshold: x > 0.5 --
+so that llTest is a Bernoulli log-likelihood in nats, comparable with the literature's binarised-MNIST figures; off = the reference's grey
+levels as soft targets) and --binarize_seed (the key of the draws, the same on every rank).
 """
 import argparse
 import json
@@ -140,6 +144,14 @@ parser.add_argument("--sample_diversity", type=int, default=0,
 parser.add_argument("--tsne", type=str, default="off", choices=["off", "host", "device"],
                     help="--plotting: add the t-SNE scatter of the prior samples (1000 per cluster) to sampled.png, embedded with sklearn on the "
                          "host (the reference's call) or with the exact t-SNE on the device (dmvae_hip.tsne.TSNE); off = the sample grid alone")
+parser.add_argument("--binarize", type=str, default="off", choices=["off", "static", "dynamic", "threshold"],
+                    help="dmvae / vade: binarise the pixels on the device (Dataset(binarize=...)) -- static: one Bernoulli draw per row (a fixed "
+                         "binarised data set); dynamic: the train set is redrawn every epoch, the test set and the --knn / --probe split keep one "
+                         "draw (Salakhutdinov & Murray 2008; Burda et al. 2016); threshold: x > 0.5 -- so that llTest is the log-probability of "
+                         "a binary data set in nats; off = grey levels as soft Bernoulli targets (the reference)")
+parser.add_argument("--binarize_seed", type=int, default=0,
+                    help="--binarize: the seed of the draws (Philox stream 8); every rank of a data-parallel run uses this same value, not a "
+                         "per-rank one: the ranks hold the whole data set and must agree on it")
 parser.add_argument("--cnn", action="store_true", default=False,
                     help="the checked-in convolutional encoder trunk (base_models.py:156,176-216) instead of the MLP branch")
 
@@ -254,13 +266,19 @@ def main(argv):
     # dmvae trains on train + test rows (train.py:205-213)
     train_data = np.concatenate([dataset.train_data, dataset.test_data], axis=0)
     train_classes = np.concatenate([dataset.train_classes, dataset.test_classes], axis=0)
-    test_data = Dataset((dataset.test_data, dataset.test_classes), batch_size=argv.batch_size)
-    train_data = Dataset((train_data, train_classes), batch_size=argv.batch_size)
+    # --binarize: the train set takes the named mode; a set that is evaluated only keeps ONE draw under "dynamic" (the protocol of Burda et al.)
+    held_out = dict(binarize="static" if argv.binarize == "dynamic" else argv.binarize, binarize_seed=argv.binarize_seed)
+    test_data = Dataset((dataset.test_data, dataset.test_classes), batch_size=argv.batch_size, **held_out)
+    train_data = Dataset((train_data, train_classes), batch_size=argv.batch_size, binarize=argv.binarize, binarize_seed=argv.binarize_seed)
 
     # --knn votes among the train split alone (train_data holds the test rows too: each would find itself) and --probe fits on it;
     # unshuffled, so that nothing is drawn from the NumPy stream and the run trains as it does without the flags
-    split_data = (Dataset((dataset.train_data, dataset.train_classes), batch_size=argv.batch_size, shuffle=False)
+    split_data = (Dataset((dataset.train_data, dataset.train_classes), batch_size=argv.batch_size, shuffle=False, **held_out)
                   if (argv.knn > 0 or argv.probe) and rank == 0 else None)
+    if argv.binarize != "off":          # make the first draw now: the host views (plots, --pretrain's mixture fit) read it back from the device
+        for ds in (test_data, train_data, split_data):
+            if ds is not None:
+                ds.device_rows(sess.device)
     knn_data = split_data if argv.knn > 0 else None
     probe_data = split_data if argv.probe else None
 
@@ -343,7 +361,8 @@ def main(argv):
                 sec = ep.pop("seconds", None)
                 rec = dict(epoch=epoch, **ep, images_per_sec=(ep.get("rows", 0) / sec if sec else None), train_seconds=sec,
                            acc_train=float(accTrain), acc_test=float(accTest), max_acc=float(max(maxAcc, accTest) if improved else maxAcc),
-                           eval_seconds=eval_seconds, eval=argv.eval, world=world, batch_size=argv.batch_size, dtype=argv.dtype, model=model_str)
+                           eval_seconds=eval_seconds, eval=argv.eval, world=world, batch_size=argv.batch_size, dtype=argv.dtype, model=model_str,
+                           binarize=argv.binarize)
                 if llTest is not None:
                     rec.update(ll_test=float(llTest), loglik_draws=argv.loglik)
                 if cmTest is not None:
@@ -402,6 +421,9 @@ def main_moe(argv, world, rank):
     import models
     from dmvae_hip import Session
     from includes.utils import MEDataset
+    if argv.binarize != "off":
+        raise ValueError("--binarize %s with --model %s: the regression labels are functions of the grey rows; the MoE data set is not binarised"
+                         % (argv.binarize, argv.model))
     if world > 1:
         raise NotImplementedError("--model %s: MoE models train on one rank" % argv.model)
     if argv.pretrain:

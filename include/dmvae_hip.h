@@ -786,6 +786,23 @@ int dmvae_prdc_counts(void* stream, const float* R, int64_t ldr, int N, const fl
 int dmvae_sinkhorn_softmin(void* stream, const float* X, int64_t ldx, int N, const float* Y, int64_t ldy, int M, int D, const float* g,
                            const float* log_b, float eps, const float* prev, float* out);
 
+/* ---- binarised rows on the device (csrc/binarize.hip): the binarised-MNIST protocol of the literature on the resident
+ * rows.  The reference has none of it: it feeds grey levels as soft Bernoulli targets.  X [n_rows][ldx] and out [n_rows][ldo]
+ * are f32 rows (unit column stride, n_cols columns used; what lies between the rows of X is not read, what lies between the rows of out is
+ * not written).  mode 0, the stochastic binarisation of Salakhutdinov & Murray 2008:
+ *   out[r][c] = u(r, c) < X[r][c] ? 1 : 0,   u = word (idx & 3) of Philox block (idx >> 2) of stream 8 at (seed, step = counter), as the uniform
+ *   (w >> 8) * 2^-24 in [0, 1),   idx = (row_base + r) * n_cols + c   in 64 bits,
+ * row_base the index of row 0 of the call in the unpermuted data set: the draw of an element depends on (seed, counter, data-set row, column)
+ * alone, so calls on chunks of the rows with their own row_base give what one call on all of them gives.  X = 0 never fires and X = 1 always
+ * does; values outside [0, 1] are no error (below 0: 0; 1 or more: 1).  mode 1, the fixed binarisation by threshold: out = X > 0.5f ? 1 : 0,
+ * no noise is read and seed / counter / row_base do not enter.  A NaN gives 0 in both modes.  One Philox block serves four consecutive idx, so
+ * n_cols need not be a multiple of 4 and no padding is asked for.  The call only enqueues and never synchronises; every argument is checked
+ * before anything is enqueued (DMVAE_EINVAL with the entry's name in the error text: a null X / out, n_rows < 1, n_cols < 1, ldx < n_cols,
+ * ldo < n_cols, row_base < 0, a mode other than 0 / 1, (row_base + n_rows) * n_cols >= 2^58 -- the block index must stay below the stream bits
+ * -- and out overlapping X: the byte spans of the two sides, first element to last, must be disjoint). */
+int dmvae_binarize_rows(void* stream, const float* X, int64_t ldx, int64_t n_rows, int n_cols, int64_t row_base, uint64_t seed, uint64_t counter,
+                        int mode, float* out, int64_t ldo);
+
 /* ---- structural similarity on the device (csrc/ssim.hip): the SSIM of Wang et al. 2004 and the squared error of
  * n_pairs comparisons of image rows.  The reference has none of it.  Comparison r reads row X[ix ? ix[r] : r] and row Y[iy ? iy[r] : r]
  * (ix, iy: device int32 [n_pairs] or NULL; X and Y may be the same buffer).  A row is `planes` images of H x W f32, one after another; ldx,
