@@ -557,6 +557,36 @@ class DeepMixtureVAE(VAE):
         acc = float(np.trace(d)) / n_test
         return (acc, d) if return_confusion else acc
 
+    def get_latent_map(self, session, data, perplexity=30.0, n_iter=1000, method="auto", trust_neighbors=5, counter=0):
+        """The map of the latent space: the t-SNE of the encoder means of ALL rows of `data` on the GPU (dmvae_hip.tsne.TSNE), with what a
+        plot colours it by.  method: "exact" (the dense P, up to 32768 rows), "knn" (P over the int(3 perplexity + 1) nearest rows, the
+        repulsion exact over all pairs, up to 2^20 rows) or "auto": exact up to 32768 rows, knn above.  Returns dict(embedding [N][2] f32,
+        classes [N], clusters [N] -- the arg-max of the scores as eval="device" takes it -- all three in the data set's current order, kl,
+        trustworthiness (sklearn.manifold.trustworthiness of the embedding against the means with trust_neighbors neighbours,
+        dmvae_hip.knn), method (what ran), n_neighbors (of the knn form, else None), seconds).  Walks the data set in its current order
+        WITHOUT reshuffling and draws nothing from the NumPy stream: the start is the device's Philox stream 5 keyed by the model's seed,
+        VaDE's responsibilities use Philox stream 2 keyed by `counter`.  Two calls return the same bits."""
+        return self._latent_map(data, self.n_classes, perplexity, n_iter, method, trust_neighbors, counter)
+
+    def _latent_map(self, data, R, perplexity, n_iter, method, trust_neighbors, counter):
+        import time
+        import torch
+        from dmvae_hip import tsne
+        if method not in ("auto", "exact", "knn"):
+            raise ValueError("method must be 'auto', 'exact' or 'knn'")
+        dev, N = self._session.device, len(data.order)
+        how = method if method != "auto" else ("exact" if N <= tsne.EXACT_MAX_N else "knn")
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        R = max(int(R), int(np.max(data._cls)) + 1)          # (the map does not need the classes to fit the clusters' matrix)
+        _, clusters = self._cluster_metrics(data, R, False, counter, True)
+        Z = self._eval_means_device(data)
+        classes = np.asarray(data._cls)[np.asarray(data.order)]
+        t = tsne.TSNE(perplexity=perplexity, n_iter=n_iter, random_state=self.seed, method=how).fit(Z)
+        trust = t.trustworthiness(Z, trust_neighbors)
+        return dict(embedding=t.embedding_, classes=classes, clusters=clusters, kl=t.kl_divergence_, trustworthiness=trust, method=how,
+                    n_neighbors=t.n_neighbors_ if how == "knn" else None, seconds=time.perf_counter() - t0)
+
     def get_cluster_exemplars(self, session, data, n=10):
         """The real rows that live in each cluster: an int array [n_classes][n] whose entry [c] holds the rows of `data`, in the data
         set's own unpermuted numbering, whose encoder means are nearest prior mean c, nearest first (a tie to the row that comes

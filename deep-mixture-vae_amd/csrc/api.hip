@@ -230,6 +230,25 @@ extern "C" int dmvae_tsne_fit(void* stream, const dmvae_tsne_config* cfg, const 
     return tsne_fit_launch((hipStream_t)stream, cfg, X, ldx, Y0, ws, ws_bytes, Y, kl);
 }
 extern "C" const float* dmvae_tsne_p(const void* ws) { return (const float*)ws; }
+extern "C" int64_t dmvae_tsne_knn_ws_bytes(const dmvae_tsne_knn_config* cfg) {
+    if (int rc = tsne_knn_check(cfg, "dmvae_tsne_knn_ws_bytes")) return rc;
+    return tsne_knn_ws_bytes(cfg);
+}
+extern "C" int dmvae_tsne_knn_cond_p(void* stream, const dmvae_tsne_knn_config* cfg, const float* d2, int64_t ldd, float* p, int64_t ldp, float* beta) {
+    return tsne_knn_cond_p_launch((hipStream_t)stream, cfg, d2, ldd, p, ldp, beta);
+}
+extern "C" int dmvae_tsne_knn_gradient(void* stream, const dmvae_tsne_knn_config* cfg, const int64_t* indptr, const int32_t* indices, const float* values,
+                                       void* ws, int64_t ws_bytes, const float* Y, float exaggeration, float* grad) {
+    return tsne_knn_gradient_launch((hipStream_t)stream, cfg, indptr, indices, values, ws, ws_bytes, Y, exaggeration, grad);
+}
+extern "C" int dmvae_tsne_knn_step(void* stream, const dmvae_tsne_knn_config* cfg, const int64_t* indptr, const int32_t* indices, const float* values,
+                                   void* ws, int64_t ws_bytes, float* Y, float* U, float* G, float exaggeration, float momentum) {
+    return tsne_knn_step_launch((hipStream_t)stream, cfg, indptr, indices, values, ws, ws_bytes, Y, U, G, exaggeration, momentum);
+}
+extern "C" int dmvae_tsne_knn_fit(void* stream, const dmvae_tsne_knn_config* cfg, const int64_t* indptr, const int32_t* indices, const float* values,
+                                  const float* Y0, void* ws, int64_t ws_bytes, float* Y, double* kl) {
+    return tsne_knn_fit_launch((hipStream_t)stream, cfg, indptr, indices, values, Y0, ws, ws_bytes, Y, kl);
+}
 extern "C" int dmvae_confusion_add(void* stream, const float* scores, int64_t ld, int n_valid, int K, const int32_t* classes, int64_t n_rows,
                                    const int32_t* perm, int64_t first, int32_t* conf, int R, int32_t* err_flag) {
     return confusion_add_launch((hipStream_t)stream, scores, ld, K, EvalRows{classes, n_rows, perm, first, n_valid, conf, R, err_flag});

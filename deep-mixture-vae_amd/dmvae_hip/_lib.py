@@ -43,6 +43,7 @@ EXPORTS = [
     "dmvae_confusion_add", "dmvae_plan_eval_clusters",
     "dmvae_plan_eval_loglik_ws_bytes", "dmvae_plan_eval_loglik",
     "dmvae_tsne_ws_bytes", "dmvae_tsne_joint_p", "dmvae_tsne_gradient", "dmvae_tsne_step", "dmvae_tsne_fit", "dmvae_tsne_p",
+    "dmvae_tsne_knn_ws_bytes", "dmvae_tsne_knn_cond_p", "dmvae_tsne_knn_gradient", "dmvae_tsne_knn_step", "dmvae_tsne_knn_fit",
     "dmvae_argmax_labels", "dmvae_silhouette_ws_bytes", "dmvae_silhouette",
     "dmvae_mixture_logpdf_ws_bytes", "dmvae_mixture_logpdf_split", "dmvae_mixture_logpdf", "dmvae_posterior_sample", "dmvae_column_stats_ws_bytes",
     "dmvae_column_stats", "dmvae_sum_f64",
@@ -82,6 +83,13 @@ class TsneConfig(C.Structure):
     """dmvae_tsne_config"""
     _fields_ = [("N", C.c_int32), ("D", C.c_int32), ("perplexity", C.c_float), ("early_exaggeration", C.c_float), ("learning_rate", C.c_float),
                 ("n_iter", C.c_int32), ("exaggeration_iters", C.c_int32), ("seed", C.c_uint64), ("flags", C.c_int32)]
+
+
+class TsneKnnConfig(C.Structure):
+    """dmvae_tsne_knn_config"""
+    _fields_ = [("N", C.c_int32), ("k", C.c_int32), ("nnz", C.c_int64), ("perplexity", C.c_float), ("early_exaggeration", C.c_float),
+                ("learning_rate", C.c_float), ("n_iter", C.c_int32), ("exaggeration_iters", C.c_int32), ("col_splits", C.c_int32),
+                ("seed", C.c_uint64), ("flags", C.c_int32)]
 
 
 class GmmSeedConfig(C.Structure):
@@ -278,6 +286,11 @@ def _load():
         "dmvae_tsne_step": [vp, P(TsneConfig), vp, i64, vp, vp, vp, f32, f32],
         "dmvae_tsne_fit": [vp, P(TsneConfig), vp, i64, vp, vp, i64, vp, vp],
         "dmvae_tsne_p": [vp],
+        "dmvae_tsne_knn_ws_bytes": [P(TsneKnnConfig)],
+        "dmvae_tsne_knn_cond_p": [vp, P(TsneKnnConfig), vp, i64, vp, i64, vp],
+        "dmvae_tsne_knn_gradient": [vp, P(TsneKnnConfig), vp, vp, vp, vp, i64, vp, f32, vp],
+        "dmvae_tsne_knn_step": [vp, P(TsneKnnConfig), vp, vp, vp, vp, i64, vp, vp, vp, f32, f32],
+        "dmvae_tsne_knn_fit": [vp, P(TsneKnnConfig), vp, vp, vp, vp, vp, i64, vp, vp],
         "dmvae_argmax_labels": [vp, vp, i64, i32, i32, vp],
         "dmvae_silhouette_ws_bytes": [i64, i32],
         "dmvae_silhouette": [vp, vp, i64, i32, i32, vp, i32, vp, i64, vp, vp, vp],
@@ -336,6 +349,7 @@ def _load():
     lib.dmvae_plan_eval_loglik_ws_bytes.restype = C.c_int64
     lib.dmvae_tsne_ws_bytes.restype = C.c_int64
     lib.dmvae_tsne_p.restype = C.c_void_p
+    lib.dmvae_tsne_knn_ws_bytes.restype = C.c_int64
     lib.dmvae_silhouette_ws_bytes.restype = C.c_int64
     lib.dmvae_mixture_logpdf_ws_bytes.restype = C.c_int64
     lib.dmvae_column_stats_ws_bytes.restype = C.c_int64

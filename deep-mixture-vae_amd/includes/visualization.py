@@ -89,13 +89,30 @@ def cluster_scatter(sample_Z, side=280, tsne="host", seed=0):
     elif Z.shape[1] > 2:
         from sklearn.manifold import TSNE
         Z = TSNE(n_components=2).fit_transform(Z)
+    return _raster(Z, np.repeat(np.arange(len(sample_Z)), n_per), side)
+
+
+def _raster(Z, labels, side):
+    """[N][2] points -> [side, side, 3]: one dot per point in colors[label % 10] on white, the labels painted in ascending order"""
+    Z, labels = np.asarray(Z, dtype=np.float64), np.asarray(labels).reshape(-1)
     lo, hi = Z.min(0), Z.max(0)
     xy = np.clip(((Z - lo) / np.maximum(hi - lo, 1e-12) * (side - 5) + 2).astype(int), 0, side - 1)
     img = np.full((side, side, 3), 255.0)
-    for k in range(len(sample_Z)):
-        pts = xy[n_per * k:n_per * (k + 1)]
-        img[side - 1 - pts[:, 1], pts[:, 0]] = _COLORS[k % 10]
+    for k in np.unique(labels):
+        pts = xy[labels == k]
+        img[side - 1 - pts[:, 1], pts[:, 0]] = _COLORS[int(k) % 10]
     return img
+
+
+def latent_map_plot(model, data, sess=None, path=None, side=560, **kw):
+    """The map every clustering-VAE paper prints: the t-SNE of the encoder means of ALL rows of `data` (model.get_latent_map, on the
+    device), drawn twice from the one embedding -- coloured by class on the left, by cluster on the right -- with cluster_scatter's
+    rasteriser and colours, to `path` (default plots/<model.name>/mnist/latent.png).  kw goes to get_latent_map (perplexity, n_iter,
+    method, ...).  Returns get_latent_map's dict."""
+    res = model.get_latent_map(sess, data, **kw)
+    left, right = _raster(res["embedding"], res["classes"], side), _raster(res["embedding"], res["clusters"], side)
+    _write_png(path or "plots/%s/mnist/latent.png" % model.name, np.concatenate([left, np.full((side, 14, 3), 255.0), right], axis=1))
+    return res
 
 
 def mnist_sample_plot(model, sess=None, tsne=False, tsne_backend="host"):

@@ -200,6 +200,12 @@ class MoE:
         self.last_linear_probe_ = self.vae.last_linear_probe_
         return res
 
+    def get_latent_map(self, session, data, perplexity=30.0, n_iter=1000, method="auto", trust_neighbors=5, counter=0):
+        """The t-SNE map of the gate's encoder means with the classes and the experts' arg-max (DeepMixtureVAE.get_latent_map), the
+        label matrix sized max(E, n_classes) as get_cluster_metrics sizes it.  No reshuffle."""
+        n_classes = int(np.max(data._cls)) + 1
+        return self.vae._latent_map(data, max(self.n_experts, n_classes), perplexity, n_iter, method, trust_neighbors, counter)
+
     def get_sample_quality(self, session, data, k=5, n_samples=None, space="latent", counter=0):
         """Precision, recall, density and coverage of the gate's decoded prior samples (DeepMixtureVAE.get_sample_quality).  No reshuffle."""
         return self.vae.get_sample_quality(session, data, k=k, n_samples=n_samples, space=space, counter=counter)

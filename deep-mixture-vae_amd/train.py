@@ -27,6 +27,9 @@ component and per class, get_sample_distance),
 --recon_quality (per epoch on the test set: SSIM, PSNR and MSE of the reconstructions, per class, get_reconstruction_quality),
 --sample_diversity N (per epoch: the mean pairwise SSIM among N decoded prior draws per mixture component, within and between components,
 get_sample_diversity; 0 = off),
+--latent_map (off | auto | exact | knn: with --plotting, latent.png -- the t-SNE map of the encoder means coloured by class and by cluster,
+get_latent_map -- of the test set at the plot epochs and of the whole train set at the end, lmTrust / lmKL in that epoch's JSONL record; knn is
+the kNN-sparse P with exact repulsion, dmvae_hip.tsne.TSNE(method="knn"), which "auto" takes above 32768 rows),
 --tsne (off | host | device: with --plotting, sampled.png gains the t-SNE scatter of the prior samples, embedded by sklearn on the CPU or by
 the exact t-SNE in HIP, dmvae_hip.tsne.TSNE),
 --binarize (off | static | dynamic | threshold; dmvae / vade: train and evaluate on binarised pixels, drawn on the device -- static: one Bernoulli
@@ -144,6 +147,11 @@ parser.add_argument("--sample_diversity", type=int, default=0,
 parser.add_argument("--tsne", type=str, default="off", choices=["off", "host", "device"],
                     help="--plotting: add the t-SNE scatter of the prior samples (1000 per cluster) to sampled.png, embedded with sklearn on the "
                          "host (the reference's call) or with the exact t-SNE on the device (dmvae_hip.tsne.TSNE); off = the sample grid alone")
+parser.add_argument("--latent_map", type=str, default="off", choices=["off", "auto", "exact", "knn"],
+                    help="--plotting: write latent.png, the t-SNE map of the encoder means coloured by class and by cluster (get_latent_map) -- of "
+                         "the test set at the plot epochs, of the whole train set at the end -- and add lmTrust / lmKL to that epoch's JSONL record; "
+                         "exact: the dense P (up to 32768 rows), knn: P over the nearest rows with exact repulsion (dmvae_hip.tsne.TSNE("
+                         "method=\"knn\")), auto: exact up to 32768 rows and knn above; rank 0 alone draws; off = no map")
 parser.add_argument("--binarize", type=str, default="off", choices=["off", "static", "dynamic", "threshold"],
                     help="dmvae / vade: binarise the pixels on the device (Dataset(binarize=...)) -- static: one Bernoulli draw per row (a fixed "
                          "binarised data set); dynamic: the train set is redrawn every epoch, the test set and the --knn / --probe split keep one "
@@ -316,9 +324,12 @@ def main(argv):
         for epoch in bar:
             if epoch % argv.save_epochs == 0 and argv.debug:
                 model.debug(sess, train_data)
+            lmTest = None
             if plotting and epoch % argv.plot_epochs == 0:      # train.py:281-286
                 visualization.mnist_sample_plot(model, sess, tsne=argv.tsne != "off", tsne_backend=argv.tsne if argv.tsne != "off" else "host")
                 visualization.mnist_regeneration_plot(model, test_data, sess)
+                if argv.latent_map != "off":
+                    lmTest = visualization.latent_map_plot(model, test_data, sess, method=argv.latent_map, counter=epoch)
             if argv.kl_annealing and (epoch + 1) % argv.anneal_epochs == 0:
                 anneal_term = min(anneal_term + argv.anneal_step, 1.0)
             loss = model.train_op(sess, train_data, anneal_term)
@@ -378,6 +389,9 @@ def main(argv):
                 if skTest is not None:
                     rec.update(_sample_distance_record(skTest))
                 rec.update(_ssim_record(rqTest, sdTest))
+                if lmTest is not None:
+                    rec.update(lmTrust=float(lmTest["trustworthiness"]), lmKL=float(lmTest["kl"]), lm_method=lmTest["method"],
+                               lm_seconds=float(lmTest["seconds"]))
                 with open(argv.model + "_metrics.jsonl", "a") as fl:
                     fl.write(json.dumps(rec) + "\n")
             if math.isnan(loss):
@@ -406,6 +420,8 @@ def main(argv):
     if plotting:                                                  # train.py:332-334
         visualization.mnist_sample_plot(model, sess, tsne=argv.tsne != "off", tsne_backend=argv.tsne if argv.tsne != "off" else "host")
         visualization.mnist_regeneration_plot(model, test_data, sess)
+        if argv.latent_map != "off":                              # the whole train set: above 32768 rows "auto" takes the knn form
+            visualization.latent_map_plot(model, train_data, sess, method=argv.latent_map, counter=argv.n_epochs)
     if rank == 0:
         with open(argv.model + "_logs.txt", "a+") as fl:
             fl.write("\n" + str(argv) + "\n------\n")

@@ -644,6 +644,47 @@ int dmvae_tsne_fit(void* stream, const dmvae_tsne_config* cfg, const float* X, i
                    double* kl);
 const float* dmvae_tsne_p(const void* ws);
 
+/* ---- kNN-sparse t-SNE on the device (csrc/tsne_knn.hip): the P of sklearn.manifold.TSNE(method="barnes_hut") with the repulsive term
+ * kept EXACT over all pairs, for N up to 2^20 (no N x N array) -------------------------------------------------------------------------
+ *   k       = min(N - 1, int(3 perplexity + 1)) <= 256, the cap of dmvae_knn (perplexity up to 85)
+ *   lists   : idx / d2 [N][k] of dmvae_knn(X, X, k, self_first = 0), ordered by (d2, j)
+ *   p_{j|i} = exp(-beta_i d'_t) / s_i over the row's k entries t, d'_t = d2[i][t] - d2[i][0], s_i = sum_t exp(-beta_i d'_t);
+ *             beta_i by the search of the dense form above: from 1, EXACTLY 64 bisection steps, s and the numerator in f64
+ *   P_ij    = (p_{j|i} + p_{i|j}) / 2N over the UNION of the lists, an absent direction counting 0, as CSR sorted by (row, column):
+ *             indptr int64 [N + 1], indices int32 [nnz], values f32 [nnz]; P_ij and P_ji are the same bits.  The library leaves this
+ *             one-off step to the caller (dmvae_hip/tsne.py: a stable sort of the int64 keys i N + j; a key occurs at most twice)
+ *   gradient: g_i = 4 [ e sum_{j in row i} P_ij q_ij (y_i - y_j) - (1 / Z) sum_{j != i} q_ij^2 (y_i - y_j) ], Z = sum_{i != j} q_ij:
+ *             the first sum over the CSR entries (a wave per row, lanes in entry order), the others over ALL pairs -- f32 sums inside
+ *             a tile of <= 1024 columns, tiles joined in tile order (the q sum in f64), the columns dealt in whole tiles to S splits
+ *             whose partials [S][N] are added in split order.  S = col_splits, or for 0: min(tiles, ceil(2048 / ceil(N / 256))).
+ *   step, fit, KL: as the dense form, the KL over the CSR entries (f64 terms) with Z from one more all-pairs pass at the final Y.
+ * dmvae_tsne_knn_fit is the start (Y0 or the Philox normals, as dmvae_tsne_fit), then n_iter times what dmvae_tsne_knn_step enqueues, then
+ * the KL: the same bits.  The calls enqueue only -- 1 launch for the conditional p, 5 per step, 6 for the KL -- and read nothing back.
+ * Every argument is checked before anything is enqueued; DMVAE_EINVAL: N outside 4 .. 2^20, perplexity outside (1, N - 1), k above 256
+ * or not the k above, n_iter or exaggeration_iters < 0, early_exaggeration or learning_rate not > 0, col_splits outside 0 .. 64,
+ * nnz < 0, flags != 0, ldd or ldp < k, a workspace too small or not 16-byte aligned, a null pointer.  Y / U / G / grad / kl / indptr
+ * 8-byte aligned.  Entries of indptr outside [0, nnz] are clamped and columns outside [0, N) skipped: nothing outside the arrays is read. */
+typedef struct dmvae_tsne_knn_config {
+    int32_t N, k;
+    int64_t nnz;             /* entries of the CSR (dmvae_tsne_knn_cond_p does not look at it) */
+    float perplexity;
+    float early_exaggeration;
+    float learning_rate;
+    int32_t n_iter;
+    int32_t exaggeration_iters;
+    int32_t col_splits;      /* 0: chosen from N                                     */
+    uint64_t seed;           /* of the Philox stream when Y0 is NULL                */
+    int32_t flags;           /* reserved: 0                                         */
+} dmvae_tsne_knn_config;
+int64_t dmvae_tsne_knn_ws_bytes(const dmvae_tsne_knn_config* cfg);      /* < 0: an error code */
+int dmvae_tsne_knn_cond_p(void* stream, const dmvae_tsne_knn_config* cfg, const float* d2, int64_t ldd, float* p, int64_t ldp, float* beta);
+int dmvae_tsne_knn_gradient(void* stream, const dmvae_tsne_knn_config* cfg, const int64_t* indptr, const int32_t* indices, const float* values,
+                            void* ws, int64_t ws_bytes, const float* Y, float exaggeration, float* grad);
+int dmvae_tsne_knn_step(void* stream, const dmvae_tsne_knn_config* cfg, const int64_t* indptr, const int32_t* indices, const float* values, void* ws,
+                        int64_t ws_bytes, float* Y, float* U, float* G, float exaggeration, float momentum);
+int dmvae_tsne_knn_fit(void* stream, const dmvae_tsne_knn_config* cfg, const int64_t* indptr, const int32_t* indices, const float* values,
+                       const float* Y0, void* ws, int64_t ws_bytes, float* Y, double* kl);
+
 /* ---- cluster quality on the device (csrc/cluster_metrics.hip): the label of every row, and the silhouette coefficient of rows under
  * labels (Rousseeuw 1987; sklearn.metrics.silhouette_samples with the Euclidean metric).  The reference reports accuracy alone. ------
  * dmvae_argmax_labels: labels[r] (device int32 [n_valid]) = the first index of the largest of row r's K scores, scores [n_valid][ld]
