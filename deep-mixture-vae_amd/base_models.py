@@ -136,9 +136,13 @@ class DeepMixtureVAE(VAE):
     def __init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=None, initializer=None,
                  cnn=False, *, batch_size=100, dtype="bf16", enc_layers=(500, 500), head_dim=2000,
                  dec_layers=(2000, 500, 500), gumbel=False, temperature=1.0, noise="device", seed=0,
-                 deterministic=True, session=None, gmm="host", eval="host", gmm_seeding="host"):
+                 deterministic=True, session=None, gmm="host", eval="host", gmm_seeding="host", label_weight=None):
         VAE.__init__(self, name, input_type, input_dim, latent_dim, activation=activation, initializer=initializer)
         self.n_classes = n_classes
+        # semi-supervised training: None = no attachment, today's plan; a number alpha attaches the cross-entropy on
+        # q(c|x) of the labelled rows (csrc/label_xent.hip) at weight alpha * N / n_labeled
+        self.label_weight = None if label_weight is None else float(label_weight)
+        self._labels_key = None
         if gmm not in ("host", "device"):
             raise ValueError("gmm must be 'host' or 'device'")
         self.gmm = gmm
@@ -192,7 +196,8 @@ class DeepMixtureVAE(VAE):
                                   dtype=self.dtype, max_batch=self.batch_size, mode="relaxed" if self.gumbel else "exact",
                                   temperature=self.temperature, seed=self.seed + 7919 * sess.rank,
                                   deterministic=self.deterministic, session=sess, cnn=self.cnn,
-                                  moe=getattr(self, "_moe_spec", None))     # (set by models.MoE: the experts' head on this gate)
+                                  moe=getattr(self, "_moe_spec", None),     # (set by models.MoE: the experts' head on this gate)
+                                  labels=self._label_placeholder(sess))
         self._engine.init_parameters(self.seed)
         # names of the graph's placeholders / tensors (fetch through the methods below)
         self.X, self.epsilon, self.cluster = "X", "epsilon_Z", "epsilon_C"
@@ -214,6 +219,37 @@ class DeepMixtureVAE(VAE):
         return self._engine
 
     # ------------------------------------------------------------------ training
+    def _label_placeholder(self, sess):
+        """the label array a plan is attached with before a data set is known: one row without a label (_bind_labels replaces it)"""
+        if self.label_weight is None:
+            return None
+        import torch
+        return torch.full((1,), -1, dtype=torch.int32, device=sess.device)
+
+    def _bind_labels(self, sess, data, train):
+        """attached plans only: the data set's label array and the term's weight for the steps that follow -- alpha * N / n_labeled in
+        train_op (over an epoch the term then estimates alpha * the mean cross-entropy of the labelled set, whatever the batch size),
+        0 in the pretraining stages.  Returns the labels' device pointer (part of train_op's recapture key)."""
+        if self.label_weight is None:
+            return None
+        if sess.world_size > 1:
+            raise NotImplementedError("label_weight: the label term is built and tested on one rank")
+        eng = self._engine
+        if train:
+            if data.labeled is None or data.n_labeled == 0:
+                raise ValueError("label_weight = %g needs a data set with labeled rows (Dataset(..., labeled=choose_labeled(...)))" % self.label_weight)
+            worst = int(np.max(np.asarray(data._cls)[data.labeled]))
+            if worst >= self.n_classes or int(np.min(np.asarray(data._cls)[data.labeled])) < 0:
+                raise ValueError("label_weight: a labeled row's class lies outside [0, n_classes = %d)" % self.n_classes)
+        labels = data.device_labels(sess.device)
+        key = (labels.data_ptr(), int(labels.shape[0]))
+        if self._labels_key != key:
+            eng.set_labels(labels)
+            self._labels_key = key
+        n_rows = int(labels.shape[0])
+        eng.set_label_weight(self.label_weight * n_rows / data.n_labeled if train else 0.0)
+        return labels.data_ptr()
+
     def _epoch_perm(self, data, sess):
         """the epoch's row order -> this rank's slice of every global batch, on the device.
         Returns (perm, n_full, tail, epoch_weight) -- see dmvae_hip.parallel.epoch_plan: with more than
@@ -244,6 +280,7 @@ class DeepMixtureVAE(VAE):
         if b != eng.max_batch:
             raise ValueError("per-rank batch %d != the size the model was built for (%d)" % (b, eng.max_batch))
         rows = data.device_rows(sess.device)
+        labels_ptr = self._bind_labels(sess, data, train=True)
         perm, n_full, tail, weight = self._epoch_perm(data, sess)
         import time
         torch.cuda.synchronize(sess.device)
@@ -264,17 +301,21 @@ class DeepMixtureVAE(VAE):
             return eps, g
 
         if host_noise:
+            if labels_ptr is not None:
+                eng.zero_label_acc()
             for i in range(n_full):
                 eps, g = host_feed(b)
                 eng.train_step(rows, perm, b, eps, g, first=i * b, grad_sync=sync, grad_scale=ex.grad_scale)
         else:
             # the captured graph holds the device pointers of the rows and of the row order: recapture
             # when either buffer (another Dataset, a re-upload) or the exchange changes
-            key = (rows.data_ptr(), perm.data_ptr(), b, sync is None)
+            key = (rows.data_ptr(), perm.data_ptr(), b, sync is None) + (() if labels_ptr is None else (labels_ptr,))
             if n_full > 0 and (self._replay is None or self._replay_key != key):
                 self._replay = eng.capture_step(rows, perm, grad_sync=sync, grad_scale=ex.grad_scale)
                 self._replay_key = key
                 eng.reset_epoch(n_full + (1 if tail else 0), kl_ratio=kl_ratio, epoch_weight=weight)
+            if labels_ptr is not None:
+                eng.zero_label_acc()                          # (behind the capture, whose warm-up steps have counted)
             for _ in range(n_full):
                 self._replay()
         if tail:                                             # the short last batch (utils.py:462-463), issued eagerly
@@ -294,6 +335,13 @@ class DeepMixtureVAE(VAE):
         n_rows = n_full * gb + tail
         self.last_epoch = dict(loss=terms[0], recon=terms[1], kl_z=terms[2], kl_c=terms[3], kl_ratio=float(kl_ratio), rows=int(n_rows),
                                steps=int(n_full + (1 if tail else 0)), seconds=(time.perf_counter() - t_wall) if t_wall is not None else None)
+        if labels_ptr is not None:
+            acc = eng.label_acc()
+            if eng.label_err():
+                raise RuntimeError("label term: error flag %d (bit 0: a label outside [0, n_classes); bit 1: a row outside the label array)" % eng.label_err())
+            # the mean cross-entropy over the labelled rows the epoch saw, how many those were, and how many of them q(c|x) already puts first
+            self.last_epoch.update(label_xent=float(acc[0] / acc[1]) if acc[1] else float("nan"), label_rows=int(acc[1]),
+                                   label_acc=float(acc[2] / acc[1]) if acc[1] else float("nan"))
         return loss
 
     # ------------------------------------------------------------------ inference pieces
@@ -411,6 +459,14 @@ class DeepMixtureVAE(VAE):
             return accuracy_from_confusion(self._device_confusion(data, order, self.n_classes), len(order))
         _, _, logits = self.encode(data.data)   # (the rows in `order`: a binarised data set presents its current draw)
         return get_clustering_accuracy(logits, data._cls[order])
+
+    def get_direct_accuracy(self, session, data):
+        """The share of rows whose arg-max cluster IS their class: the trace of the [cluster][class] confusion matrix over N -- no
+        matching.  With labels tying cluster c to class c (label_weight) this is the number that matters; get_accuracy stays the
+        Hungarian one.  The matrix is the one _device_confusion builds on the GPU, whatever `eval` says.  No reshuffle."""
+        order = data.order
+        conf = np.asarray(self._device_confusion(data, order, self.n_classes))
+        return float(np.trace(conf)) / max(1, len(order))
 
     def get_log_likelihood(self, session, data, k=50, counter=0):
         """Held-out log-likelihood of `data` in nats per row: the importance-weighted bound (Burda et al., 2016) with k draws of Z per
@@ -858,6 +914,7 @@ class DeepMixtureVAE(VAE):
         if data.batch_size % world or b != eng.max_batch:
             raise ValueError("batch_size %d does not match the model (%d per rank x %d ranks)" % (data.batch_size, eng.max_batch, world))
         rows = data.device_rows(sess.device)
+        self._bind_labels(sess, data, train=False)             # (an attached plan pretrains at w = 0)
         perm, n_full, tail, weight = self._epoch_perm(data, sess)
         import time
         torch.cuda.synchronize(sess.device)
@@ -970,7 +1027,10 @@ class VaDE(DeepMixtureVAE):
 
     def __init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=None, initializer=None, cnn=False, *,
                  batch_size=100, dtype="bf16", enc_layers=(2000, 500, 500), dec_layers=(500, 500, 2000), noise="device", seed=0,
-                 deterministic=True, session=None, gmm="host", eval="host", gmm_seeding="host"):
+                 deterministic=True, session=None, gmm="host", eval="host", gmm_seeding="host", label_weight=None):
+        if label_weight is not None:
+            raise NotImplementedError("VaDE(label_weight=...): VaDE's q(c|x) is p(c|z) -- a gradient on it runs through Z into the VaDE "
+                                      "latent stage, which has no such input")
         if cnn and tuple(enc_layers) == (2000, 500, 500):
             enc_layers = (128,)            # base_models.py:486: ("fc", {"input_dim": 2048, "output_dim": 128})
         DeepMixtureVAE.__init__(self, name, input_type, input_dim, latent_dim, n_classes, activation=activation, initializer=initializer,

@@ -24,6 +24,7 @@
 #include "binarize.h"
 #include "ssim.h"
 #include "probe.h"
+#include "label_xent.h"
 #include "measure.h"
 
 namespace dmvae {
@@ -252,6 +253,18 @@ extern "C" int dmvae_tsne_knn_fit(void* stream, const dmvae_tsne_knn_config* cfg
 extern "C" int dmvae_confusion_add(void* stream, const float* scores, int64_t ld, int n_valid, int K, const int32_t* classes, int64_t n_rows,
                                    const int32_t* perm, int64_t first, int32_t* conf, int R, int32_t* err_flag) {
     return confusion_add_launch((hipStream_t)stream, scores, ld, K, EvalRows{classes, n_rows, perm, first, n_valid, conf, R, err_flag});
+}
+extern "C" int64_t dmvae_label_xent_acc_elems(int n_valid) { return label_xent_acc_elems(n_valid); }
+extern "C" int dmvae_label_xent(void* stream, const float* logits, int64_t ld_lg, int n_valid, int K, const int32_t* labels, int64_t label_rows,
+                                const int32_t* perm, int64_t first, float scale, int act_dtype, void* dlogits, int64_t ld_dl, float* row_loss,
+                                double* acc, int32_t* err_flag) {
+    LabelXentArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = logits; a.ld_lg = ld_lg; a.n_valid = n_valid; a.K = K;
+    a.labels = labels; a.label_rows = label_rows; a.perm = perm; a.first = first;
+    a.act_dtype = act_dtype; a.scale = scale;
+    a.dlogits = dlogits; a.ld_dl = ld_dl; a.row_loss = row_loss; a.acc = acc; a.err_flag = err_flag;
+    return label_xent_launch((hipStream_t)stream, a, "dmvae_label_xent");
 }
 extern "C" int dmvae_argmax_labels(void* stream, const float* scores, int64_t ld, int n_valid, int K, int32_t* labels) {
     return argmax_labels_launch((hipStream_t)stream, scores, ld, n_valid, K, labels);

@@ -128,6 +128,14 @@ struct dmvae_plan {
         int nblk = 0;
         const int32_t* perm = nullptr; int64_t first = 0; const void* st = nullptr;     // the batch's rows (recorded by the batch loads)
     } moe;
+    // semi-supervised label attachment (dmvae_plan_attach_labels): the cross-entropy stage of label_xent.hip behind the latent stage.  No
+    // parameter, no GEMM problem; the workspace grows by the three buffers below.  The batch's rows are the ones moe.perm / first / st record.
+    struct {
+        bool on = false;
+        const int32_t* labels = nullptr; int64_t rows = 0;
+        int64_t o_ctl = 0, o_acc = 0, o_err = 0;     // "label_ctl" (f32: [0] = w), "label_acc" (float64 [acc_elems]), "label_err" (int32)
+        int64_t acc_elems = 0;
+    } lab;
 };
 
 static inline int pad64(int x) { return (x + 63) / 64 * 64; }
@@ -170,6 +178,7 @@ int fwd_dense(dmvae_plan* p, hipStream_t s, const PAct& in, const PLayer& L, int
 int encode_impl(dmvae_plan* p, hipStream_t s, bool heads = true);
 int decode_hidden(dmvae_plan* p, hipStream_t s);
 int moe_stage(dmvae_plan* p, hipStream_t s, int n_valid, float inv_B, bool backward);
+int label_stage(dmvae_plan* p, hipStream_t s, int n_valid, float inv_B);
 int conv_dw_split(int64_t K, int tiles);
 int conv_layer_dw(hipStream_t s, int dt, int M, int P, int cin, int kdim, const void* in, int64_t cin_ld, const void* dact, int64_t cout_ld,
                   int cout_np, int cout, int sp, float* slab, float* dW, float* db);

@@ -5,6 +5,7 @@
 
 #include "plan.h"
 #include "moe_head.h"
+#include "label_xent.h"
 
 using namespace dmvae;
 
@@ -285,6 +286,7 @@ extern "C" int dmvae_plan_bind(dmvae_plan* p, const dmvae_buffers* b) {
 extern "C" int dmvae_plan_attach_moe(dmvae_plan* p, const dmvae_moe_config* m) {
     DMVAE_REQUIRE(p && m, "dmvae_plan_attach_moe: null argument");
     DMVAE_REQUIRE(!p->bound && !p->moe.on, "dmvae_plan_attach_moe: attach once, before dmvae_plan_bind");
+    if (p->lab.on) { set_error("dmvae_plan_attach_moe: not on a plan with a label attachment (dmvae_plan_attach_labels)"); return DMVAE_EUNSUPPORTED; }
     if (p->vade || !p->conv.empty() || p->dw_slices_max > 1) {
         set_error("dmvae_plan_attach_moe: the MoE head runs on DMVAE plans with the MLP trunk and fewer than 8192 rows (VaDE: its gate p(c|z) "
                   "sends gradients through Z; conv trunk: the flat input is not resident; larger batches: dW K-slices)");
@@ -339,6 +341,38 @@ extern "C" int dmvae_plan_moe_set_labels(dmvae_plan* p, const float* labels, int
     return 0;
 }
 
+// Semi-supervised label attachment (label_xent.hip): no parameter, no GEMM problem -- the workspace grows by the control word, the
+// accumulators (with the stage's partials, sized for the padded batch) and the error flag.
+extern "C" int dmvae_plan_attach_labels(dmvae_plan* p, const dmvae_label_config* m) {
+    DMVAE_REQUIRE(p && m, "dmvae_plan_attach_labels: null argument");
+    DMVAE_REQUIRE(!p->bound && !p->lab.on, "dmvae_plan_attach_labels: attach once, before dmvae_plan_bind");
+    if (p->vade) {
+        set_error("dmvae_plan_attach_labels: not on a VaDE plan (its q(c|x) is p(c|z): the gradient would run through Z into the VaDE latent stage)");
+        return DMVAE_EUNSUPPORTED;
+    }
+    if (p->moe.on) {
+        set_error("dmvae_plan_attach_labels: not on a plan with a MoE attachment (its loss already owns the gate's labels)");
+        return DMVAE_EUNSUPPORTED;
+    }
+    DMVAE_REQUIRE(m->labels && m->label_rows > 0 && m->reserved == 0, "dmvae_plan_attach_labels: null labels / label_rows=%lld / reserved != 0", (long long)m->label_rows);
+    auto& L = p->lab;
+    L.labels = m->labels; L.rows = m->label_rows;
+    int64_t w = p->work_bytes;
+    L.o_ctl = take(w, 256);
+    L.acc_elems = label_xent_acc_elems(p->Bp);
+    L.o_acc = take(w, L.acc_elems * 8);
+    L.o_err = take(w, 256);
+    p->work_bytes = w;
+    L.on = true;
+    return 0;
+}
+
+extern "C" int dmvae_plan_set_labels(dmvae_plan* p, const int32_t* labels, int64_t label_rows) {
+    DMVAE_REQUIRE(p && p->lab.on && labels && label_rows > 0, "dmvae_plan_set_labels: no label attachment / null labels");
+    p->lab.labels = labels; p->lab.rows = label_rows;
+    return 0;
+}
+
 extern "C" int dmvae_plan_set_stage_groups(dmvae_plan* p, int n_groups) {
     DMVAE_REQUIRE(p && (n_groups == 2 || n_groups == 3), "dmvae_plan_set_stage_groups: 2 or 3 weight-gradient launches per staged backward");
     p->stage_groups = n_groups;
@@ -360,6 +394,12 @@ extern "C" int dmvae_plan_view(const dmvae_plan* p, const char* name, void** ptr
     const auto& a = p->a;
     const PAct* v = nullptr;
     PAct half;
+    if (p->lab.on && (n == "label_ctl" || n == "label_acc" || n == "label_err")) {      // the label attachment's words: not [Bp][cols] activations
+        *ptr = WS(p, n == "label_ctl" ? p->lab.o_ctl : n == "label_acc" ? p->lab.o_acc : p->lab.o_err);
+        *ld = n == "label_acc" ? p->lab.acc_elems : 1;
+        *dtype = n == "label_ctl" ? DMVAE_F32 : n == "label_acc" ? DMVAE_F64 : DMVAE_I32;
+        return 0;
+    }
     if (n == "mean") v = &a.mv;
     else if (n == "log_var") { half = a.mv.sub(p->Dp, p->Dp); v = &half; }
     else if (n == "logits") v = &a.lg;

@@ -4,6 +4,7 @@
 
 #include "plan.h"
 #include "moe_head.h"
+#include "label_xent.h"
 #include "measure.h"
 
 using namespace dmvae;
@@ -90,6 +91,7 @@ extern "C" int dmvae_plan_swap_batch(dmvae_plan* p) {
     p->tsrc.data = p->pf.data; p->tsrc.n_rows = p->pf.n_rows; p->tsrc.perm = p->pf.perm; p->tsrc.first = p->pf.first; p->tsrc.n_valid = p->pf.n_valid;
     p->tsrc.st = p->pf.st;
     p->tsrc_valid = true; p->tsrc_used = false;
+    p->moe.perm = p->pf.perm; p->moe.first = p->pf.first; p->moe.st = p->pf.st;      // the current batch's rows (the label stage reads them)
     p->pf.armed = p->pf.done = false;
     return 0;
 }
@@ -450,6 +452,24 @@ int dmvae::moe_stage(dmvae_plan* p, hipStream_t s, int n_valid, float inv_B, boo
     return grad_dense(p, s, fl ? M.inp : XB(p), M.dP, M.L);
 }
 
+// The label stage of a pass, behind the latent stage (which has written logits and dlogits): the cross-entropy on q(c|x) of the labelled rows
+// added into dlogits before the heads' backward reads it (label_xent.hip).  One launch; the weight w is read on the device.
+int dmvae::label_stage(dmvae_plan* p, hipStream_t s, int n_valid, float inv_B) {
+    const auto& L = p->lab;
+    LabelXentArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = WSf(p, p->a.lg); a.ld_lg = p->a.lg.ld;
+    a.n_valid = n_valid; a.K = p->cfg.n_classes;
+    a.labels = L.labels; a.label_rows = L.rows;
+    a.perm = p->moe.perm; a.first = p->moe.first; a.batch = p->cfg.max_batch; a.st = reinterpret_cast<const dmvae_state*>(p->moe.st);
+    a.act_dtype = p->cfg.dtype;
+    a.scale = inv_B; a.w = WSf(p, L.o_ctl);
+    a.dlogits = WS(p, p->a.dlg); a.ld_dl = p->a.dlg.ld;
+    a.acc = reinterpret_cast<double*>(WS(p, L.o_acc));
+    a.err_flag = reinterpret_cast<int32_t*>(WS(p, L.o_err));
+    return label_xent_launch(s, a, "dmvae_plan_forward_backward (label stage)");
+}
+
 // ====================================================================== the pass
 // What one forward + backward pass decides once, before its first launch.
 struct Pass {
@@ -625,6 +645,7 @@ static int forward_and_loss(dmvae_plan* p, Pass& ps) {
     if (ps.hl_fused) TRY(heads_latent_stage(p, ps));
     else TRY(latent_launch(ps.s, &ps.la));
     if (p->moe.on) TRY(moe_stage(p, ps.s, ps.n_valid, ps.inv_B, true));
+    if (p->lab.on) TRY(label_stage(p, ps.s, ps.n_valid, ps.inv_B));
     TRY(decode_hidden(p, ps.s));
     TRY(output_layer_recon(p, ps));
     if (ps.fin_rides) return 0;

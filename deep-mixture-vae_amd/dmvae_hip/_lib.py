@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("DMVAE_HIP_LIB") or os.path.join(_HERE, "libdmvae_hip.
 
 ABI_VERSION = 5          # DMVAE_ABI_VERSION of include/dmvae_hip.h
 F32, BF16 = 0, 1
+F64, I32 = 2, 3        # DMVAE_F64 / DMVAE_I32: the dtype codes of the "label_acc" / "label_err" views
 EUNSUPPORTED = -2        # DMVAE_EUNSUPPORTED
 ADAM_ZERO_GRAD, ADAM_IEEE, ADAM_SHADOW = 1, 2, 4
 GEMM_FWD, GEMM_DX, GEMM_DW = 0, 1, 2
@@ -38,6 +39,7 @@ EXPORTS = [
     "dmvae_plan_bind", "dmvae_plan_load_batch", "dmvae_plan_load_batch_step", "dmvae_plan_prefetch_batch", "dmvae_plan_swap_batch", "dmvae_plan_forward_backward",
     "dmvae_plan_update", "dmvae_plan_encode", "dmvae_plan_decode", "dmvae_plan_view",
     "dmvae_plan_attach_moe", "dmvae_plan_moe_set_labels", "dmvae_plan_moe_predict",
+    "dmvae_label_xent_acc_elems", "dmvae_label_xent", "dmvae_plan_attach_labels", "dmvae_plan_set_labels",
     "dmvae_gmm_ws_bytes", "dmvae_gmm_fit", "dmvae_gmm_kmeans",
     "dmvae_gmm_seed_ws_bytes", "dmvae_gmm_seed", "dmvae_philox_uniform",
     "dmvae_confusion_add", "dmvae_plan_eval_clusters",
@@ -64,6 +66,11 @@ class MoeConfig(C.Structure):
     """dmvae_moe_config: the mixture-of-experts attachment of a plan"""
     _fields_ = [("n_experts", C.c_int32), ("output_dim", C.c_int32), ("featLearn", C.c_int32), ("classification", C.c_int32),
                 ("lossVAE", C.c_int32), ("reserved", C.c_int32), ("labels", C.c_void_p), ("label_rows", C.c_int64)]
+
+
+class LabelConfig(C.Structure):
+    """dmvae_label_config: the semi-supervised label attachment of a plan"""
+    _fields_ = [("labels", C.c_void_p), ("label_rows", C.c_int64), ("reserved", C.c_int64)]
 
 
 class GmmConfig(C.Structure):
@@ -270,6 +277,10 @@ def _load():
         "dmvae_plan_attach_moe": [vp, P(MoeConfig)],
         "dmvae_plan_moe_set_labels": [vp, vp, i64],
         "dmvae_plan_moe_predict": [vp, vp, i32],
+        "dmvae_label_xent_acc_elems": [i32],
+        "dmvae_label_xent": [vp, vp, i64, i32, i32, vp, i64, vp, i64, f32, i32, vp, i64, vp, vp, vp],
+        "dmvae_plan_attach_labels": [vp, P(LabelConfig)],
+        "dmvae_plan_set_labels": [vp, vp, i64],
         "dmvae_gmm_ws_bytes": [P(GmmConfig)],
         "dmvae_gmm_fit": [vp, P(GmmConfig), vp, i64, vp, vp, vp, vp, i64, P(GmmResult)],
         "dmvae_gmm_kmeans": [vp, P(GmmConfig), vp, i64, vp, vp, i64, P(GmmResult)],
@@ -355,6 +366,7 @@ def _load():
     lib.dmvae_column_stats_ws_bytes.restype = C.c_int64
     lib.dmvae_knn_ws_bytes.restype = C.c_int64
     lib.dmvae_softmax_xent_ws_bytes.restype = C.c_int64
+    lib.dmvae_label_xent_acc_elems.restype = C.c_int64
     lib.dmvae_plan_destroy.restype = None
     got = lib.dmvae_abi_version()
     if got != ABI_VERSION:       # the public structs grew between versions: a mismatched pair would read past them

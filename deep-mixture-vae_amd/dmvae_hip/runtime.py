@@ -111,7 +111,7 @@ class StepEngine:
     def __init__(self, input_dim, latent_dim, n_classes, enc_layers=(500, 500), head_dim=2000,
                  dec_layers=(2000, 500, 500), input_type="binary", dtype="bf16", max_batch=100,
                  mode="exact", temperature=1.0, seed=0, deterministic=False, session=None,
-                 beta1=0.9, beta2=0.999, adam_eps=1e-8, cnn=False, model="dmvae", adam_ieee=False, moe=None):
+                 beta1=0.9, beta2=0.999, adam_eps=1e-8, cnn=False, model="dmvae", adam_ieee=False, moe=None, labels=None):
         self.cnn = bool(cnn)
         self.model = model
         if model not in ("dmvae", "vade"):
@@ -157,6 +157,7 @@ class StepEngine:
         # moe: dict(n_experts, output_dim, featLearn, classification, lossVAE, labels = device f32 [rows, output_dim]):
         # the mixture-of-experts head of models.py (dmvae_plan_attach_moe), attached before the plan's sizes are read
         self.moe = None
+        class_labels = labels                       # (the MoE branch below has its own `labels`)
         if moe is not None:
             labels = moe["labels"]
             assert labels.dtype == torch.float32 and labels.is_contiguous() and labels.dim() == 2 and labels.shape[1] == int(moe["output_dim"])
@@ -167,6 +168,16 @@ class StepEngine:
             check(lib.dmvae_plan_attach_moe(self._plan, C.byref(mc)), "dmvae_plan_attach_moe")
             self.moe = dict(moe)
             self._moe_labels = labels               # keep alive
+        # labels: device int32 [rows], the class of the rows that carry a label and -1 elsewhere: the semi-supervised cross-entropy on
+        # q(c|x) (dmvae_plan_attach_labels), attached before the plan's sizes are read.  Its weight starts at 0 (set_label_weight).
+        self.labels = None
+        labels = class_labels
+        if labels is not None:
+            assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 1
+            lc = _lib.LabelConfig()
+            lc.labels, lc.label_rows, lc.reserved = labels.data_ptr(), labels.shape[0], 0
+            check(lib.dmvae_plan_attach_labels(self._plan, C.byref(lc)), "dmvae_plan_attach_labels")
+            self.labels = labels                    # keep alive
         sz = _lib.Sizes()
         check(lib.dmvae_plan_sizes(self._plan, C.byref(sz)), "dmvae_plan_sizes")
         self.sizes = sz
@@ -289,6 +300,38 @@ class StepEngine:
         st = self.read_state()
         self.write_state(adam_t=0, noise_step=0, kl_ratio=st.kl_ratio, lr=st.lr)
 
+    # ------------------------------------------------------------ semi-supervised labels
+    def _label_view(self, name, nbytes, dtype):
+        if self.labels is None:
+            raise RuntimeError("this StepEngine has no label attachment (labels=...)")
+        p, ld, dt = C.c_void_p(), C.c_int64(), C.c_int32()
+        check(lib.dmvae_plan_view(self._plan, name, C.byref(p), C.byref(ld), C.byref(dt)), "dmvae_plan_view")
+        off = p.value - self.work.data_ptr()
+        return self.work[off: off + nbytes].view(dtype)
+
+    def set_labels(self, labels):
+        """another int32 label array (-1 = no label) for the following steps (host state only: a captured step keeps its own)"""
+        assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 1
+        if self.labels is None:
+            raise RuntimeError("this StepEngine has no label attachment (labels=...)")
+        self.labels = labels
+        check(lib.dmvae_plan_set_labels(self._plan, ptr(labels), labels.shape[0]), "dmvae_plan_set_labels")
+
+    def set_label_weight(self, w):
+        """w of the label term, written into the "label_ctl" view: the kernel reads it there, so captured steps follow"""
+        self._label_view(b"label_ctl", 4, torch.float32).fill_(float(w))
+
+    def label_acc(self):
+        """[epoch sum of l_r, epoch labelled rows, epoch rows whose arg-max is their label, then the same three of the last batch] (float64)"""
+        return self._label_view(b"label_acc", 48, torch.float64).cpu().numpy()
+
+    def zero_label_acc(self):
+        self._label_view(b"label_acc", 48, torch.float64).zero_()
+
+    def label_err(self):
+        """the stage's error flag: bit 0 a label outside {-1} u [0, K), bit 1 a row index outside the label array"""
+        return int(self._label_view(b"label_err", 4, torch.int32).item())
+
     # ------------------------------------------------------------ mixture of experts
     def moe_acc(self):
         """the attachment's accumulators: [epoch loss_moe sum, epoch error sum, last batch loss_moe, last batch error] (host floats)"""
@@ -369,8 +412,8 @@ class StepEngine:
         assert perm is None or (perm.dtype == torch.int32 and perm.is_contiguous())
         n_valid = self.max_batch if n_valid is None else int(n_valid)
         self._pf_primed = False
-        if self.moe is not None:
-            # the MoE stage of the passes that follow reads its labels through `perm` (step.hip: batch_rows keeps the pointer): a temporary
+        if self.moe is not None or self.labels is not None:
+            # the MoE stage / the label stage of the passes that follow reads its labels through `perm` (step.hip: batch_rows keeps the pointer): a temporary
             # would go back to the allocator here and be handed to the caller's next tensor (eps, gumbel) before the pass has run
             self._batch_src = (data, perm)
         check(lib.dmvae_plan_load_batch(self._plan, self._stream(), ptr(data), data.shape[0], ptr(perm),

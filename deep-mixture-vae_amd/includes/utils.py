@@ -149,6 +149,28 @@ def _device_classes(ds, device):
 BINARIZE_MODES = ("off", "static", "dynamic", "threshold")
 
 
+def choose_labeled(classes, n_labeled, n_classes, seed, rows=None):
+    """Stratified choice of the rows that keep their label (semi-supervised training): class c gets
+    n_labeled // n_classes rows, the remainder goes to the lowest classes one each.  The draw is per class, in ascending class order, from
+    np.random.RandomState(seed): the global NumPy stream is never touched, so a run shuffles and samples as it did.  rows: draw among
+    these row indices only (train.py: the train split's).  Returns the sorted int64 row indices; a class with fewer rows than its quota
+    raises ValueError."""
+    classes = np.asarray(classes)
+    n_labeled, n_classes = int(n_labeled), int(n_classes)
+    if n_labeled < 0 or n_classes < 1:
+        raise ValueError("choose_labeled: n_labeled = %d, n_classes = %d" % (n_labeled, n_classes))
+    pool = np.arange(len(classes)) if rows is None else np.asarray(rows, dtype=np.int64)
+    rng = np.random.RandomState(int(seed))
+    picked = []
+    for c in range(n_classes):
+        quota = n_labeled // n_classes + (1 if c < n_labeled % n_classes else 0)
+        mine = pool[classes[pool] == c]
+        if len(mine) < quota:
+            raise ValueError("choose_labeled: class %d has %d rows, its quota is %d" % (c, len(mine), quota))
+        picked.append(np.sort(mine[rng.permutation(len(mine))[:quota]]))
+    return np.sort(np.concatenate(picked)).astype(np.int64) if picked else np.zeros(0, dtype=np.int64)
+
+
 class Dataset:
     """includes/utils.py:428-466.  Same contract: shuffle on construction and at
     every get_batches() with the global NumPy RNG, consecutive batches, short
@@ -162,12 +184,16 @@ class Dataset:
     device (dmvae_hip.binarize) into a second resident buffer that device_rows returns in place of the grey rows; binarize_seed keys it, and
     the ranks of a data-parallel run pass the same one: they hold the whole data set and must agree on it.  No NumPy draw is consumed."""
 
-    def __init__(self, data, batch_size=100, shuffle=True, binarize="off", binarize_seed=0):
+    def __init__(self, data, batch_size=100, shuffle=True, binarize="off", binarize_seed=0, labeled=None):
         data, classes = data
         if binarize not in BINARIZE_MODES:
             raise ValueError("binarize = %r: one of %s" % (binarize, ", ".join(BINARIZE_MODES)))
         self._rows = np.ascontiguousarray(np.asarray(data, dtype=np.float32))
         self._cls = np.copy(classes)
+        # labeled: indices (choose_labeled) of the UNPERMUTED rows whose class a semi-supervised model may see; a reshuffle moves nothing
+        self.labeled = None if labeled is None else np.unique(np.asarray(labeled, dtype=np.int64))
+        if self.labeled is not None and len(self.labeled) and (self.labeled[0] < 0 or self.labeled[-1] >= len(self._rows)):
+            raise ValueError("Dataset: labeled row indices outside [0, %d)" % len(self._rows))
         self.order = np.arange(len(self._rows))
         self.batch_size = batch_size
         self.shuffle = shuffle
@@ -245,6 +271,25 @@ class Dataset:
 
     def device_classes(self, device):
         return _device_classes(self, device)
+
+    @property
+    def n_labeled(self):
+        return 0 if self.labeled is None else int(len(self.labeled))
+
+    def host_labels(self):
+        """int32 [N] in the unpermuted row order: the class at the labeled rows, -1 elsewhere"""
+        y = np.full(len(self._rows), -1, dtype=np.int32)
+        if self.n_labeled:
+            y[self.labeled] = np.asarray(self._cls)[self.labeled].astype(np.int32)
+        return y
+
+    def device_labels(self, device):
+        """host_labels() resident next to device_rows (uploaded once)"""
+        import torch
+        key = "labels:" + str(device)
+        if key not in self._device:
+            self._device[key] = torch.as_tensor(self.host_labels()).to(device)
+        return self._device[key]
 
     def __len__(self):
         return self.epoch_len

@@ -35,7 +35,12 @@ the exact t-SNE in HIP, dmvae_hip.tsne.TSNE),
 --binarize (off | static | dynamic | threshold; dmvae / vade: train and evaluate on binarised pixels, drawn on the device -- static: one Bernoulli
 draw of every row; dynamic: a fresh draw of the train set per epoch, the test set and the --knn / --probe split static; threshold: x > 0.5 --
 so that llTest is a Bernoulli log-likelihood in nats, comparable with the literature's binarised-MNIST figures; off = the reference's grey
-levels as soft targets) and --binarize_seed (the key of the draws, the same on every rank).
+levels as soft targets) and --binarize_seed (the key of the draws, the same on every rank),
+--n_labeled L / --label_weight A / --label_seed S (dmvae, one rank: semi-supervised training -- L rows of the train split, stratified by
+class, keep their label and every step adds A * N / L * the cross-entropy of q(c|x) = softmax(logits) on the labelled rows of its batch
+(csrc/label_xent.hip), which pulls cluster c onto class c; the epoch line gains accDirect, the share of test rows whose arg-max cluster IS
+their class (get_direct_accuracy), the JSONL acc_direct_test, label_xent, label_rows, label_acc, n_labeled, label_weight; 0 = off, and then
+the plan and the run are what they were; refused with --model vade | dmoe | dvmoe and with more than one rank).
 """
 import argparse
 import json
@@ -157,6 +162,12 @@ parser.add_argument("--binarize", type=str, default="off", choices=["off", "stat
                          "binarised data set); dynamic: the train set is redrawn every epoch, the test set and the --knn / --probe split keep one "
                          "draw (Salakhutdinov & Murray 2008; Burda et al. 2016); threshold: x > 0.5 -- so that llTest is the log-probability of "
                          "a binary data set in nats; off = grey levels as soft Bernoulli targets (the reference)")
+parser.add_argument("--n_labeled", type=int, default=0,
+                    help="dmvae, one rank: semi-supervised training -- this many rows of the TRAIN split keep their class (stratified, "
+                         "includes.utils.choose_labeled) and a cross-entropy on q(c|x) pulls cluster c onto class c (csrc/label_xent.hip); 0 = off")
+parser.add_argument("--label_weight", type=float, default=1.0,
+                    help="--n_labeled: alpha, the weight of the mean cross-entropy of the labelled set against the per-row VAE loss")
+parser.add_argument("--label_seed", type=int, default=0, help="--n_labeled: the seed of the stratified draw (its own RandomState)")
 parser.add_argument("--binarize_seed", type=int, default=0,
                     help="--binarize: the seed of the draws (Philox stream 8); every rank of a data-parallel run uses this same value, not a "
                          "per-rank one: the ranks hold the whole data set and must agree on it")
@@ -230,6 +241,13 @@ def main(argv):
     np.random.seed(argv.seed)
 
     model_str, model_name = argv.model, argv.model_name
+    if argv.n_labeled < 0:
+        raise ValueError("--n_labeled must be >= 0")
+    if argv.n_labeled > 0 and model_str != "dmvae":
+        raise NotImplementedError("--n_labeled: the label term acts on DMVAE's q(c|x) = softmax(logits); VaDE's q(c|x) is p(c|z) (the gradient would "
+                                  "run through Z into the VaDE latent stage) and the MoE models have their own supervised loss")
+    if argv.n_labeled > 0 and world > 1:
+        raise NotImplementedError("--n_labeled: the label term is built and tested on one rank")
     if model_str in ("dmoe", "dvmoe"):
         return main_moe(argv, world, rank)
     if model_str == "vademoe":
@@ -268,7 +286,8 @@ def main(argv):
             batch_size=argv.batch_size // world, dtype=argv.dtype,
             enc_layers=[int(v) for v in argv.enc_layers.split(",")], head_dim=argv.head_dim,
             dec_layers=[int(v) for v in argv.dec_layers.split(",")], gumbel=argv.gumbel, temperature=argv.temperature,
-            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, gmm=argv.gmm, eval=argv.eval, gmm_seeding=argv.gmm_seeding
+            noise="host" if argv.host_noise else "device", seed=argv.seed, session=sess, gmm=argv.gmm, eval=argv.eval, gmm_seeding=argv.gmm_seeding,
+            label_weight=argv.label_weight if argv.n_labeled > 0 else None
         ).build_graph()
 
     # dmvae trains on train + test rows (train.py:205-213)
@@ -277,7 +296,13 @@ def main(argv):
     # --binarize: the train set takes the named mode; a set that is evaluated only keeps ONE draw under "dynamic" (the protocol of Burda et al.)
     held_out = dict(binarize="static" if argv.binarize == "dynamic" else argv.binarize, binarize_seed=argv.binarize_seed)
     test_data = Dataset((dataset.test_data, dataset.test_classes), batch_size=argv.batch_size, **held_out)
-    train_data = Dataset((train_data, train_classes), batch_size=argv.batch_size, binarize=argv.binarize, binarize_seed=argv.binarize_seed)
+    # --n_labeled: drawn from the train split's rows only (the first len(train split) rows of train_data): the test rows train unlabelled
+    labeled = None
+    if argv.n_labeled > 0:
+        from includes.utils import choose_labeled
+        labeled = choose_labeled(train_classes, argv.n_labeled, n_clusters, argv.label_seed, rows=np.arange(len(dataset.train_data)))
+    train_data = Dataset((train_data, train_classes), batch_size=argv.batch_size, binarize=argv.binarize, binarize_seed=argv.binarize_seed,
+                         labeled=labeled)
 
     # --knn votes among the train split alone (train_data holds the test rows too: each would find itself) and --probe fits on it;
     # unshuffled, so that nothing is drawn from the NumPy stream and the run trains as it does without the flags
@@ -337,7 +362,8 @@ def main(argv):
             accTrain = model.get_accuracy(sess, train_data)
             accTest = model.get_accuracy(sess, test_data)
             eval_seconds = time.perf_counter() - t_eval
-            llTest = model.get_log_likelihood(sess, test_data, k=argv.loglik, counter=epoch) if argv.loglik > 0 else None
+            accDirect = model.get_direct_accuracy(sess, test_data) if argv.n_labeled > 0 else None      # (no reshuffle: the NumPy stream stays put)
+            llTest =model.get_log_likelihood(sess, test_data, k=argv.loglik, counter=epoch) if argv.loglik > 0 else None
             cmTest = model.get_cluster_metrics(sess, test_data, counter=epoch) if argv.metrics else None
             # (rank 0 alone: the call holds no collective and every rank would compute the same figures)
             pdTest = model.get_posterior_diagnostics(sess, test_data, counter=epoch) if argv.diagnostics and rank == 0 else None
@@ -374,6 +400,8 @@ def main(argv):
                            acc_train=float(accTrain), acc_test=float(accTest), max_acc=float(max(maxAcc, accTest) if improved else maxAcc),
                            eval_seconds=eval_seconds, eval=argv.eval, world=world, batch_size=argv.batch_size, dtype=argv.dtype, model=model_str,
                            binarize=argv.binarize)
+                if accDirect is not None:      # (label_xent / label_rows / label_acc are in last_epoch)
+                    rec.update(acc_direct_test=float(accDirect), n_labeled=argv.n_labeled, label_weight=argv.label_weight)
                 if llTest is not None:
                     rec.update(ll_test=float(llTest), loglik_draws=argv.loglik)
                 if cmTest is not None:
@@ -398,6 +426,8 @@ def main(argv):
                 raise FloatingPointError("loss is NaN at epoch %d (the reference drops into pdb here, train.py:320-321)" % epoch)
             postfix = {"loss": "%.4f" % loss, "accTrain": "%.4f" % accTrain, "accTest": "%.4f" % accTest,
                        "maxAcc": "%.4f" % maxAcc, "accClusteringTest": "%.4f" % accTest}
+            if accDirect is not None:
+                postfix["accDirect"] = "%.4f" % accDirect
             if llTest is not None:
                 postfix["llTest"] = "%.4f" % llTest
             if cmTest is not None:

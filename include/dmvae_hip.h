@@ -476,6 +476,54 @@ int dmvae_plan_moe_set_labels(dmvae_plan* p, const float* labels, int64_t label_
  * (reconstructed_Y_soft / reconstructed_Y) and adds loss and error to the accumulators; no gradient, no state change */
 int dmvae_plan_moe_predict(dmvae_plan* p, void* stream, int n_valid);
 
+/* ---- semi-supervised DMVAE: cross-entropy on q(c|x) = softmax(logits) for the batch rows that carry a label (label_xent.hip) ----
+ * Batch row r < n_valid is data-set row i_r = perm[first + r] (perm NULL: first + r); its label y_r = labels[i_r], labels a device
+ * int32 [label_rows] array in data-set row order, -1 = no label.  For the labelled rows
+ *     l_r = logsumexp(logits_r[0..K)) - logits_r[y_r]               (f32, the maximum subtracted)
+ *     dlogits_r[k] += coefficient * (softmax(logits_r)[k] - [k == y_r])      (act dtype: f32 add, then round to nearest even)
+ * and NOTHING else of dlogits is written: rows without a label, rows >= n_valid, columns >= K keep their bits, and every row does while
+ * the coefficient is zero.  A label outside {-1} u [0, K) sets bit 0 of *err_flag, a row index outside [0, label_rows) bit 1 (device
+ * int32, the caller zeroes it); such a row is skipped and nothing is read out of bounds (the rule of dmvae_plan_eval_clusters).
+ *
+ * dmvae_label_xent: the stage alone on caller buffers; the launcher the plan calls.  coefficient = scale.  row_loss (may be NULL):
+ *   f32 [n_valid], l_r, 0 in rows without a label.  acc: device float64 [dmvae_label_xent_acc_elems(n_valid)], zeroed ONCE by the caller:
+ *   [0] += sum of l_r (unweighted), [1] += labelled rows, [2] += rows whose arg-max (np.argmax's rule on ties: the first index of the
+ *   largest, as dmvae_argmax_labels) equals the label; [3..6) = the same three of this launch alone; [6..8) and the rest are the launch's
+ *   scratch (tickets, one partial triple per workgroup of four rows), which must be zero when a launch starts and which every launch
+ *   leaves zero again: zero the buffer once, then only [0..6) as needed.  Counts are exact (< 2^53); the
+ *   partials are added in workgroup order by the last workgroup to arrive: no float atomics, two runs give the same bits.  One launch
+ *   (none when n_valid == 0); it only enqueues.  Every argument is checked by name before anything is enqueued (DMVAE_EINVAL): a null
+ *   logits / labels / dlogits / acc / err_flag, K < 1, n_valid < 0, ld_lg < K, ld_dl < K, label_rows < 1, first < 0, without perm
+ *   first + n_valid > label_rows, act_dtype not DMVAE_F32 / DMVAE_BF16, a scale that is not finite.
+ *
+ * dmvae_plan_attach_labels: between dmvae_plan_create and dmvae_plan_sizes / bind, like dmvae_plan_attach_moe.  Every pass of the plan
+ *   then runs the stage behind its latent stage (one launch more; a plan without the attachment enqueues what it always did) on its own
+ *   logits / dlogits with coefficient = w * inv_B (inv_B as passed to the pass, not scaled by kl_ratio), so the term reaches the c-head and
+ *   the trunk and nothing else.  w is READ ON THE DEVICE from the "label_ctl" view (f32, [0] = w, written by the caller; 0 after the
+ *   caller's zeroing of the workspace): a captured step follows a change of w without recapture.  Rows are addressed as the last batch load
+ *   addressed them (device cursor included): a captured step needs no per-step host argument.  Views: "label_ctl"; "label_acc" (float64,
+ *   the layout of acc above, ld = its element count; the caller zeroes it); "label_err" (int32, the error flag).  No new parameter, no
+ *   new GEMM problem; the workspace grows only on attached plans.  Attaches to MLP and conv trunks, f32 and bf16, exact and relaxed KL
+ *   mode, every batch size.  DMVAE_EUNSUPPORTED: VaDE plans (their q(c|x) is p(c|z): the gradient would run through Z into the VaDE
+ *   latent stage) and plans with a MoE attachment (and dmvae_plan_attach_moe refuses a plan with labels).
+ *   Staged backward (dmvae_plan_forward_backward_stage) is SERVED: the stage belongs to segment 0.  Prefetched batches
+ *   (dmvae_plan_prefetch_batch) are SERVED too: the stage reads the cursor of the current batch, which step_finalize advances later in
+ *   the same pass, and dmvae_plan_swap_batch hands the prefetched batch's rows on.
+ * dmvae_plan_set_labels: another label array for the following passes (host state only; a captured step keeps its own). */
+#define DMVAE_F64 2      /* dtype code of the "label_acc" view */
+#define DMVAE_I32 3      /* dtype code of the "label_err" view */
+typedef struct dmvae_label_config {
+    const int32_t* labels;   /* device int32 [label_rows], -1 = no label */
+    int64_t label_rows;
+    int64_t reserved;        /* 0 */
+} dmvae_label_config;
+int64_t dmvae_label_xent_acc_elems(int n_valid);
+int dmvae_label_xent(void* stream, const float* logits, int64_t ld_lg, int n_valid, int K, const int32_t* labels, int64_t label_rows,
+                     const int32_t* perm, int64_t first, float scale, int act_dtype, void* dlogits, int64_t ld_dl, float* row_loss,
+                     double* acc, int32_t* err_flag);
+int dmvae_plan_attach_labels(dmvae_plan* p, const dmvae_label_config* cfg);
+int dmvae_plan_set_labels(dmvae_plan* p, const int32_t* labels, int64_t label_rows);
+
 /* ---- diagonal-covariance Gaussian mixture fit (the GMM initialisation of the prior tables, base_models.py:367-390, 614-646:
  * sklearn.mixture.GaussianMixture(covariance_type="diag")) ------------------------------------------------------------------
  * EM over X [N][ldx] f32 with n_init restarts side by side in one call; sklearn's semantics:
