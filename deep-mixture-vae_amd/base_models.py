@@ -613,6 +613,52 @@ class DeepMixtureVAE(VAE):
         acc = float(np.trace(d)) / n_test
         return (acc, d) if return_confusion else acc
 
+    def get_few_label_accuracy(self, session, train_data, test_data, n_labeled=100, seed=0, k=7, alpha=0.8, weights="connectivity", labeled=None):
+        """Given this latent space and only n_labeled labels, how many test rows end up with the right class -- and how much of that comes
+        from the unlabelled rows?  Label spreading (Zhou et al. 2004; dmvae_hip.spread, csrc/label_spread.hip) over ONE symmetric k-nearest-
+        neighbour graph of the encoder means of the train rows followed by the test rows, both in the data sets' own unpermuted numbering.
+        Labels: the rows choose_labeled(train classes, n_labeled, n_classes, seed) of the train data and nobody else; labeled: these row
+        indices instead (Dataset.labeled of a semi-supervised run).  Returns dict(accuracy: over the test rows; accuracy_unlabeled_train:
+        over the train rows without a label; n_unreached: rows of the graph no label reaches -- they count as wrong; n_iter, change: of
+        the iteration; per_class: the test accuracy per class (nan for a class without test rows); knn1 and probe: on the SAME labels and
+        nothing else, the test accuracy of the 1-nearest-neighbour classifier and of the linear probe fitted on the labelled means alone
+        -- accuracy minus these is what the unlabelled geometry adds; n_labeled).  No reshuffle, nothing drawn from the NumPy stream, no
+        parameter or step state written.  ValueError when a class lacks its quota of rows or k does not fit the rows."""
+        import torch
+        from dmvae_hip import knn, probe, spread
+        from includes.utils import choose_labeled
+        n_train, n_test = len(train_data.order), len(test_data.order)
+        cls_x, cls_q = np.asarray(train_data._cls).astype(np.int64), np.asarray(test_data._cls).astype(np.int64)
+        R = int(max(np.max(cls_x), np.max(cls_q))) + 1
+        if labeled is None:
+            labeled = choose_labeled(cls_x, n_labeled, R, seed)
+        labeled = np.unique(np.asarray(labeled, dtype=np.int64))
+        if len(labeled) < 1 or labeled[0] < 0 or labeled[-1] >= n_train:
+            raise ValueError("get_few_label_accuracy: the labelled rows must be train rows in [0, %d), one at least" % n_train)
+        Z = torch.empty((n_train + n_test, self.latent_dim), dtype=torch.float32, device=self._session.device)
+        for data, at in ((train_data, 0), (test_data, n_train)):
+            for s, n in self._eval_batches(data, np.arange(len(data.order))):
+                self._engine.encode(n)
+                Z[at + s:at + s + n].copy_(self._engine.view("mean", n))
+        y = np.full(n_train + n_test, -1, dtype=np.int64)
+        y[labeled] = cls_x[labeled]
+        ls = spread.LabelSpreading(n_neighbors=k, alpha=alpha, weights=weights).fit(Z, y)
+        self.last_label_spreading_ = ls
+        truth = np.concatenate([cls_x, cls_q])
+        ok = ls.transduction_ == truth
+        free = np.ones(n_train, dtype=bool)
+        free[labeled] = False
+        per_class = [float(np.mean(ok[n_train:][cls_q == c])) if np.any(cls_q == c) else float("nan") for c in range(R)]
+        Zl, Zq, yl = Z[torch.as_tensor(labeled, device=Z.device)], Z[n_train:], cls_x[labeled]
+        knn1 = knn.KNeighborsClassifier(n_neighbors=1).fit(Zl, yl).score(Zq, cls_q)
+        if len(np.unique(yl)) >= 2:
+            lin = float(np.mean(probe.LogisticRegression(C=1.0, tol=1e-4, max_iter=200, standardize=True).fit(Zl, yl).predict(Zq) == cls_q))
+        else:
+            lin = float(np.mean(cls_q == yl[0]))                     # one class among the labels: the probe has nothing to separate
+        return dict(accuracy=float(np.mean(ok[n_train:])), accuracy_unlabeled_train=float(np.mean(ok[:n_train][free])) if free.any() else float("nan"),
+                    n_unreached=ls.n_unreached_, n_iter=ls.n_iter_, change=ls.change_, per_class=per_class, knn1=knn1, probe=lin,
+                    n_labeled=int(len(labeled)))
+
     def get_latent_map(self, session, data, perplexity=30.0, n_iter=1000, method="auto", trust_neighbors=5, counter=0):
         """The map of the latent space: the t-SNE of the encoder means of ALL rows of `data` on the GPU (dmvae_hip.tsne.TSNE), with what a
         plot colours it by.  method: "exact" (the dense P, up to 32768 rows), "knn" (P over the int(3 perplexity + 1) nearest rows, the

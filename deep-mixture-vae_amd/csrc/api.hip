@@ -25,6 +25,7 @@
 #include "ssim.h"
 #include "probe.h"
 #include "label_xent.h"
+#include "label_spread.h"
 #include "measure.h"
 
 namespace dmvae {
@@ -328,6 +329,16 @@ extern "C" int dmvae_softmax_xent(void* stream, const float* Z, int64_t ldz, int
 extern "C" int dmvae_linear_scores(void* stream, const float* Z, int64_t ldz, int M, int D, const float* shift, const float* scale, const float* W, int64_t ldw,
                                    const float* b, int C, float* scores, int64_t lds) {
     return probe_scores_launch((hipStream_t)stream, Z, ldz, M, D, shift, scale, W, ldw, b, C, scores, lds);
+}
+extern "C" int dmvae_graph_sym_normalize(void* stream, const int64_t* indptr, const int32_t* indices, const float* w, int N, int64_t nnz, float* s, float* r,
+                                         int32_t* err_flag) {
+    return graph_sym_normalize_launch((hipStream_t)stream, indptr, indices, w, N, nnz, s, r, err_flag);
+}
+extern "C" int64_t dmvae_label_spread_ws_bytes(int64_t N, int C) { return label_spread_ws_bytes(N, C); }
+extern "C" int dmvae_label_spread(void* stream, const int64_t* indptr, const int32_t* indices, const float* s, int N, int64_t nnz, const int32_t* labels, int C,
+                                  float alpha, int n_iter, const float* F_in, int64_t ld_in, float* F, int64_t ldf, float* change, void* ws,
+                                  int64_t ws_bytes, int32_t* err_flag) {
+    return label_spread_launch((hipStream_t)stream, indptr, indices, s, N, nnz, labels, C, alpha, n_iter, F_in, ld_in, F, ldf, change, ws, ws_bytes, err_flag);
 }
 extern "C" int dmvae_recon_nblocks(int B_pad, int I_pad) { return recon_nblocks(B_pad, I_pad); }
 extern "C" int dmvae_recon_fwd_bwd(void* stream, int act_dtype, int recon_kind, int B, int B_pad, int I, int I_pad, const float* logits,

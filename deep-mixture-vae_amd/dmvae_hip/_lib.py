@@ -55,6 +55,7 @@ EXPORTS = [
     "dmvae_binarize_rows",
     "dmvae_ssim_rows",
     "dmvae_softmax_xent_ws_bytes", "dmvae_softmax_xent", "dmvae_linear_scores",
+    "dmvae_graph_sym_normalize", "dmvae_label_spread_ws_bytes", "dmvae_label_spread",
     "dmvae_prof_enable", "dmvae_prof_collect", "dmvae_debug_spin", "dmvae_debug_strip_fwd2", "dmvae_debug_stamps", "dmvae_debug_anatomy", "dmvae_debug_anatomy256", "dmvae_debug_set_tile", "dmvae_debug_set_knob", "dmvae_abi_version", "dmvae_last_error",
     "dmvae_debug_conv_first_fwd", "dmvae_debug_conv_first_dw", "dmvae_debug_zero_border", "dmvae_debug_maxpool2_fwd", "dmvae_debug_maxpool2_bwd_relu",
     "dmvae_debug_conv_wflip", "dmvae_debug_conv_gemm", "dmvae_debug_conv_dw",
@@ -323,6 +324,9 @@ def _load():
         "dmvae_softmax_xent_ws_bytes": [i64, i32, i32],
         "dmvae_softmax_xent": [vp, vp, i64, i64, i32, vp, vp, vp, i32, vp, i64, vp, vp, i64, vp, vp],
         "dmvae_linear_scores": [vp, vp, i64, i32, i32, vp, vp, vp, i64, vp, i32, vp, i64],
+        "dmvae_graph_sym_normalize": [vp, vp, vp, vp, i32, i64, vp, vp, vp],
+        "dmvae_label_spread_ws_bytes": [i64, i32],
+        "dmvae_label_spread": [vp, vp, vp, vp, i32, i64, vp, i32, f32, i32, vp, i64, vp, i64, vp, vp, i64, vp],
         "dmvae_prof_enable": [i32],
         "dmvae_debug_spin": [vp, i32],
         "dmvae_debug_strip_fwd2": [vp, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64],
@@ -367,6 +371,7 @@ def _load():
     lib.dmvae_knn_ws_bytes.restype = C.c_int64
     lib.dmvae_softmax_xent_ws_bytes.restype = C.c_int64
     lib.dmvae_label_xent_acc_elems.restype = C.c_int64
+    lib.dmvae_label_spread_ws_bytes.restype = C.c_int64
     lib.dmvae_plan_destroy.restype = None
     got = lib.dmvae_abi_version()
     if got != ABI_VERSION:       # the public structs grew between versions: a mismatched pair would read past them

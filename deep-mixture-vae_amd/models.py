@@ -200,6 +200,15 @@ class MoE:
         self.last_linear_probe_ = self.vae.last_linear_probe_
         return res
 
+    def get_few_label_accuracy(self, session, train_data, test_data, n_labeled=100, seed=0, k=7, alpha=0.8, weights="connectivity", labeled=None):
+        """Few-label accuracy of the gate's encoder means by label spreading (DeepMixtureVAE.get_few_label_accuracy).  No reshuffle."""
+        if self.vae is None:
+            raise NotImplementedError("get_few_label_accuracy: %s has no encoder to take latent means from" % type(self).__name__)
+        res = self.vae.get_few_label_accuracy(session, train_data, test_data, n_labeled=n_labeled, seed=seed, k=k, alpha=alpha, weights=weights,
+                                              labeled=labeled)
+        self.last_label_spreading_ = self.vae.last_label_spreading_
+        return res
+
     def get_latent_map(self, session, data, perplexity=30.0, n_iter=1000, method="auto", trust_neighbors=5, counter=0):
         """The t-SNE map of the gate's encoder means with the classes and the experts' arg-max (DeepMixtureVAE.get_latent_map), the
         label matrix sized max(E, n_classes) as get_cluster_metrics sizes it.  No reshuffle."""

@@ -20,6 +20,8 @@ New flags (defaults = reference behaviour): --batch_size, --dtype, --seed,
 --knn K (per epoch: the accuracy of a K-nearest-neighbour vote among the train split's latent means on the test set's, get_knn_accuracy; 0 = off),
 --probe / --probe_C (per epoch: the accuracy on the test set of a linear probe -- multinomial logistic regression, inverse penalty probe_C --
 fitted on the train split's latent means, get_linear_probe_accuracy),
+--few_label L / --few_label_seed (per epoch: the test accuracy of label spreading over the nearest-neighbour graph of the train split's and the
+test set's latent means from L stratified labels of the train split, get_few_label_accuracy; 0 = off),
 --sample_quality K (per epoch on the test set: improved precision / recall and density / coverage of the decoded draws from the mixture prior,
 K-th-neighbour balls, per prior component and per class, get_sample_quality; 0 = off),
 --sample_distance (per epoch on the test set: the Sinkhorn divergence between the decoded draws from the mixture prior and the data, per prior
@@ -131,6 +133,15 @@ parser.add_argument("--probe", action="store_true", default=False,
                          "multinomial logistic regression fitted on the encoder means of the train split, loss and gradient on the device "
                          "(get_linear_probe_accuracy); rank 0 alone evaluates")
 parser.add_argument("--probe_C", type=float, default=1.0, help="--probe: the inverse of the L2 penalty, as sklearn's C")
+parser.add_argument("--few_label", type=int, default=0,
+                    help="L > 0 adds flTest to the epoch line -- given this latent space and only L labels of the train split (stratified, "
+                         "includes.utils.choose_labeled), how many test rows get the right class: label spreading over the nearest-neighbour "
+                         "graph of the train split's and the test set's encoder means on the device (get_few_label_accuracy), with the "
+                         "1-nearest-neighbour and linear-probe accuracies on the same L labels alone in the JSONL record; rank 0 alone "
+                         "evaluates; 0 = off")
+parser.add_argument("--few_label_seed", type=int, default=0,
+                    help="--few_label: the seed of the stratified draw; the default is --label_seed's, so --n_labeled L --few_label L evaluates "
+                         "with exactly the labels the training saw")
 parser.add_argument("--sample_quality", type=int, default=0,
                     help="K > 0 adds precTest and covTest to the epoch line -- are the decoded draws from the mixture prior realistic, and do they "
                          "cover the test set: improved precision / recall and density / coverage with K-th-neighbour balls in the space of the "
@@ -173,6 +184,13 @@ parser.add_argument("--binarize_seed", type=int, default=0,
                          "per-rank one: the ranks hold the whole data set and must agree on it")
 parser.add_argument("--cnn", action="store_true", default=False,
                     help="the checked-in convolutional encoder trunk (base_models.py:156,176-216) instead of the MLP branch")
+
+
+def _few_label_record(fl):
+    """the JSONL keys of --few_label"""
+    return dict(few_label_test=float(fl["accuracy"]), few_label_unlabeled_train=float(fl["accuracy_unlabeled_train"]), few_label_knn1=float(fl["knn1"]),
+                few_label_probe=float(fl["probe"]), few_label_unreached=int(fl["n_unreached"]), few_label_iters=int(fl["n_iter"]),
+                few_label_n=int(fl["n_labeled"]))
 
 
 def _metrics_record(cm):
@@ -307,13 +325,14 @@ def main(argv):
     # --knn votes among the train split alone (train_data holds the test rows too: each would find itself) and --probe fits on it;
     # unshuffled, so that nothing is drawn from the NumPy stream and the run trains as it does without the flags
     split_data = (Dataset((dataset.train_data, dataset.train_classes), batch_size=argv.batch_size, shuffle=False, **held_out)
-                  if (argv.knn > 0 or argv.probe) and rank == 0 else None)
+                  if (argv.knn > 0 or argv.probe or argv.few_label > 0) and rank == 0 else None)
     if argv.binarize != "off":          # make the first draw now: the host views (plots, --pretrain's mixture fit) read it back from the device
         for ds in (test_data, train_data, split_data):
             if ds is not None:
                 ds.device_rows(sess.device)
     knn_data = split_data if argv.knn > 0 else None
     probe_data = split_data if argv.probe else None
+    few_data = split_data if argv.few_label > 0 else None
 
     model.define_train_step(argv.init_lr, train_data.epoch_len * argv.decay_epochs, argv.decay_rate)
 
@@ -369,6 +388,8 @@ def main(argv):
             pdTest = model.get_posterior_diagnostics(sess, test_data, counter=epoch) if argv.diagnostics and rank == 0 else None
             knnTest = model.get_knn_accuracy(sess, knn_data, test_data, k=argv.knn) if knn_data is not None else None
             probeTest = model.get_linear_probe_accuracy(sess, probe_data, test_data, C=argv.probe_C) if probe_data is not None else None
+            flTest = (model.get_few_label_accuracy(sess, few_data, test_data, n_labeled=argv.few_label, seed=argv.few_label_seed)
+                      if few_data is not None else None)
             sqTest = model.get_sample_quality(sess, test_data, k=argv.sample_quality, counter=epoch) if argv.sample_quality > 0 and rank == 0 else None
             skTest = model.get_sample_distance(sess, test_data, counter=epoch) if argv.sample_distance and rank == 0 else None
             rqTest = model.get_reconstruction_quality(sess, test_data) if argv.recon_quality and rank == 0 else None
@@ -412,6 +433,8 @@ def main(argv):
                     rec.update(knnTest=float(knnTest), knn_k=argv.knn)
                 if probeTest is not None:
                     rec.update(probeTest=float(probeTest), probe_C=argv.probe_C, probe_iters=model.last_linear_probe_.n_iter_)
+                if flTest is not None:
+                    rec.update(_few_label_record(flTest))
                 if sqTest is not None:
                     rec.update(_sample_quality_record(sqTest))
                 if skTest is not None:
@@ -438,6 +461,8 @@ def main(argv):
                 postfix["knnTest"] = "%.4f" % knnTest
             if probeTest is not None:
                 postfix["probeTest"] = "%.4f" % probeTest
+            if flTest is not None:
+                postfix["flTest"] = "%.4f" % flTest["accuracy"]
             if sqTest is not None:
                 postfix.update(precTest="%.4f" % sqTest["precision"], covTest="%.4f" % sqTest["coverage"])
             if skTest is not None:
@@ -517,6 +542,8 @@ def main_moe(argv, world, rank):
         cmTest = model.get_cluster_metrics(sess, test_data, counter=epoch) if argv.metrics else None
         knnTest = model.get_knn_accuracy(sess, train_data, test_data, k=argv.knn) if argv.knn > 0 else None
         probeTest = model.get_linear_probe_accuracy(sess, train_data, test_data, C=argv.probe_C) if argv.probe else None
+        flTest = (model.get_few_label_accuracy(sess, train_data, test_data, n_labeled=argv.few_label, seed=argv.few_label_seed)
+                  if argv.few_label > 0 else None)
         sqTest = model.get_sample_quality(sess, test_data, k=argv.sample_quality, counter=epoch) if argv.sample_quality > 0 else None
         skTest = model.get_sample_distance(sess, test_data, counter=epoch) if argv.sample_distance else None
         rqTest = model.get_reconstruction_quality(sess, test_data) if argv.recon_quality else None
@@ -536,6 +563,8 @@ def main_moe(argv, world, rank):
             rec.update(knnTest=float(knnTest), knn_k=argv.knn)
         if probeTest is not None:
             rec.update(probeTest=float(probeTest), probe_C=argv.probe_C, probe_iters=model.last_linear_probe_.n_iter_)
+        if flTest is not None:
+            rec.update(_few_label_record(flTest))
         if sqTest is not None:
             rec.update(_sample_quality_record(sqTest))
         if skTest is not None:

@@ -943,6 +943,32 @@ int dmvae_softmax_xent(void* stream, const float* Z, int64_t ldz, int64_t n, int
 int dmvae_linear_scores(void* stream, const float* Z, int64_t ldz, int M, int D, const float* shift, const float* scale, const float* W, int64_t ldw,
                         const float* b, int C, float* scores, int64_t lds);
 
+/* ---- label spreading on a sparse symmetric graph (csrc/label_spread.hip): the hot path of the few-label evaluator
+ * (Zhou et al. 2004, Learning with local and global consistency).  The reference has none of it.  The graph W is CSR on the device -- indptr
+ * int64 [N + 1], indices int32 [nnz] ascending within a row, values f32 [nnz] -- symmetric and without a diagonal: what the union of the lists
+ * of dmvae_knn(X, X, k, self_first = 0) gives.  Whatever indptr holds, only entries [0, nnz) are read.
+ * dmvae_graph_sym_normalize: d_i = sum_j W_ij in float64 in CSR order, r_i = d_i^-1/2 rounded once to f32 (exactly 0 for a row without edges;
+ *   r f32 [N]), s_ij = (W_ij r_i) r_j in f32 (s f32 [nnz], the layout of w).  A column index outside [0, N) ORs bit 0 into *err_flag (device
+ *   int32); that entry adds nothing to d_i, gets s = 0 and nothing is read through it.  Two launches.
+ * dmvae_label_spread: n_iter >= 1 iterations F <- alpha S F + (1 - alpha) Y, one launch each, Y the one-hot of labels (device int32 [N], -1:
+ *   no label) over C classes.  Per element acc = fmaf(s_ij, F[j][c], acc) over the row's entries ascending, from 0, then
+ *   F'[i][c] = fmaf(alpha, acc, (1 - alpha) [labels_i == c]) with 1 - alpha rounded once: a function of the inputs alone, whatever the launch
+ *   shape.  F_in (device f32 [N][ld_in], ld_in >= C; NULL: zeros) is the start -- the F of an earlier call, the same buffer included, continues
+ *   it bit for bit; the result lands in F [N][ldf], ldf >= C, whose columns >= C keep their bits.  change[t] (device f32 [n_iter]) =
+ *   max_ic |F^(t+1) - F^t|, joined from per-wave maxima in integer order (no float atomics; a NaN in F gives a NaN); nothing past n_iter entries
+ *   is written.  A label outside {-1} u [0, C) ORs bit 1 into *err_flag and the row counts as unlabelled; a column index outside [0, N) ORs bit 0
+ *   and the entry is skipped.  ws: the caller's scratch of dmvae_label_spread_ws_bytes(N, C) bytes (host arithmetic), 16-byte aligned: two
+ *   copies of F with C padded to a multiple of 4 and the per-wave maxima.  No host synchronisation, no cooperative launch, no spinning: the
+ *   kernel boundary is the only ordering between workgroups.
+ * Domain: 1 <= N <= 2^20, 2 <= C <= 1024, 0 < alpha < 1, any row degree.  Both only enqueue; every argument is checked before anything is
+ * enqueued (DMVAE_EINVAL with the entry's name in the error text); rows are indexed in 64 bits; two calls return the same bits. */
+int dmvae_graph_sym_normalize(void* stream, const int64_t* indptr, const int32_t* indices, const float* w, int N, int64_t nnz, float* s, float* r,
+                              int32_t* err_flag);
+int64_t dmvae_label_spread_ws_bytes(int64_t N, int C);                     /* < 0: an error code */
+int dmvae_label_spread(void* stream, const int64_t* indptr, const int32_t* indices, const float* s, int N, int64_t nnz, const int32_t* labels, int C,
+                       float alpha, int n_iter, const float* F_in, int64_t ld_in, float* F, int64_t ldf, float* change, void* ws, int64_t ws_bytes,
+                       int32_t* err_flag);
+
 /* Measurement and tuning entry points (per-kernel timing for bench.py's roofline leg, probes, tile knobs) are
  * declared in dmvae_hip_debug.h: exported by the same library, not part of the drop-in boundary. */
 int dmvae_abi_version(void);
