@@ -279,7 +279,7 @@ class DeepMixtureVAE(VAE):
         b = gb // world                                       # per-rank batch
         if b != eng.max_batch:
             raise ValueError("per-rank batch %d != the size the model was built for (%d)" % (b, eng.max_batch))
-        rows = data.device_rows(sess.device)
+        rows = data.train_rows(sess.device)                    # (device_rows itself unless the data set augments: DESIGN.md section 30)
         labels_ptr = self._bind_labels(sess, data, train=True)
         perm, n_full, tail, weight = self._epoch_perm(data, sess)
         import time
@@ -522,6 +522,57 @@ class DeepMixtureVAE(VAE):
             if 2 <= int(used) <= N - 1:
                 res["silhouette"] = total / N
         return (res, labels.cpu().numpy()) if return_labels else res
+
+    def get_augmentation_consistency(self, session, data, augment, n_draws=4, seed=0, counter=0):
+        """Does a row keep its cluster when it is perturbed?  dict(agree, agree_per_class, acc_clean, acc_aug, n, n_draws) of `data` under
+        the random affine maps of `augment` (an AugmentSpec or its string; dmvae_hip.augment, csrc/augment.hip).  One clean pass over the
+        resident rows in their current order -- labels through eval_labels, the confusion matrix through eval_clusters -- then, for every
+        draw j, the rows warped into ONE scratch buffer under Philox counter counter * n_draws + j and the same batches from it.  agree: the
+        share of (row, draw) pairs whose arg-max cluster equals the clean one; agree_per_class: the same per class of the row (nan for a
+        class without rows); acc_aug: the accuracy of the warped rows under the CLEAN rows' Hungarian matching, so a drop is a drop and not
+        a re-matching.  No reshuffle, nothing drawn from NumPy; VaDE's responsibilities use the device noise of get_cluster_metrics, the
+        same for the clean and the warped rows.  The label comparisons are integer ops on the device; everything comes back in one read."""
+        import torch
+        from scipy.optimize import linear_sum_assignment
+        from dmvae_hip.augment import augment as warp, parse_augment
+        spec, J = parse_augment(augment), int(n_draws)
+        if J < 1:
+            raise ValueError("n_draws = %d: at least one draw" % J)
+        eng, dev, R = self._engine, self._session.device, self.n_classes
+        order = data.order
+        N = len(order)
+        cls = data.device_classes(dev)
+        rows = self._eval_order_on_device(data, order)
+        spec.shape_for(rows.shape[1])
+        confs = torch.zeros((J + 1, R * R + 1), dtype=torch.int32, device=dev)
+        labels = torch.empty((J + 1, N), dtype=torch.int32, device=dev)
+        scratch = torch.empty_like(rows)
+
+        def walk(src, j):
+            for s in range(0, N, eng.max_batch):
+                n = min(eng.max_batch, N - s)
+                eng.load_batch(src, self._eval_perm, s, n)
+                eng.eval_clusters(confs[j], cls, self._eval_perm, s, n, draws=self._metrics_draws, eps=None, counter=counter)
+                eng.eval_labels(labels[j, s:s + n], n)
+        walk(rows, 0)
+        for j in range(J):
+            warp(rows, spec, seed=seed, counter=int(counter) * J + j, out=scratch)
+            walk(scratch, j + 1)
+        same = (labels[1:] == labels[:1]).sum(dim=0, dtype=torch.int64)                  # [N]: the draws that kept the row's cluster
+        c = cls[self._eval_perm.long()].long()
+        ok = ((c >= 0) & (c < R)).long()                                                  # (a class outside [0, R) is flagged by eval_clusters)
+        c = c.clamp(0, R - 1)
+        per = torch.zeros(2 * R, dtype=torch.int64, device=dev)
+        per[:R].index_add_(0, c, same * ok)
+        per[R:].index_add_(0, c, ok)
+        host = torch.cat([confs.reshape(-1).long(), per, same.sum().reshape(1)]).cpu().numpy()       # the one read
+        mats = [eng.read_confusion(torch.as_tensor(host[j * (R * R + 1):(j + 1) * (R * R + 1)].astype(np.int32))) for j in range(J + 1)]
+        per = host[(J + 1) * (R * R + 1):]
+        r, col = linear_sum_assignment(mats[0].max() - mats[0])                           # accuracy_from_confusion's matching, kept for the warped rows
+        with np.errstate(invalid="ignore", divide="ignore"):
+            per_class = per[:R] / (per[R:2 * R] * float(J))
+        return dict(agree=float(per[2 * R]) / (N * J), agree_per_class=[float(x) for x in per_class],
+                    acc_clean=float(mats[0][r, col].sum()) / N, acc_aug=float(sum(m[r, col].sum() for m in mats[1:])) / (N * J), n=int(N), n_draws=J)
 
     def get_posterior_diagnostics(self, session, data, counter=0, max_points=None, au_threshold=0.01, eps=None, return_points=False):
         """What the KL term bought: dict(mi, marginal_kl, rate, mi_cap, active_units, var_of_mean, mean_of_var, n_points, n_rows) of
@@ -959,7 +1010,7 @@ class DeepMixtureVAE(VAE):
         b = data.batch_size // world
         if data.batch_size % world or b != eng.max_batch:
             raise ValueError("batch_size %d does not match the model (%d per rank x %d ranks)" % (data.batch_size, eng.max_batch, world))
-        rows = data.device_rows(sess.device)
+        rows = data.train_rows(sess.device)                    # (device_rows itself unless the data set augments: DESIGN.md section 30)
         self._bind_labels(sess, data, train=False)             # (an attached plan pretrains at w = 0)
         perm, n_full, tail, weight = self._epoch_perm(data, sess)
         import time

@@ -22,6 +22,7 @@
 #include "prdc.h"
 #include "sinkhorn.h"
 #include "binarize.h"
+#include "augment.h"
 #include "ssim.h"
 #include "probe.h"
 #include "label_xent.h"
@@ -315,6 +316,10 @@ extern "C" int dmvae_sinkhorn_softmin(void* stream, const float* X, int64_t ldx,
 extern "C" int dmvae_binarize_rows(void* stream, const float* X, int64_t ldx, int64_t n_rows, int n_cols, int64_t row_base, uint64_t seed, uint64_t counter,
                                    int mode, float* out, int64_t ldo) {
     return binarize_rows_launch((hipStream_t)stream, X, ldx, n_rows, n_cols, row_base, seed, counter, mode, out, ldo);
+}
+extern "C" int dmvae_augment_rows(void* stream, const float* X, int64_t ldx, int64_t n_rows, int H, int W, int64_t row_base, uint64_t seed, uint64_t counter,
+                                  const dmvae_augment_params* p, const float* theta_in, float* theta_out, float* out, int64_t ldo) {
+    return augment_rows_launch((hipStream_t)stream, X, ldx, n_rows, H, W, row_base, seed, counter, p, theta_in, theta_out, out, ldo);
 }
 extern "C" int dmvae_ssim_rows(void* stream, const float* X, int64_t ldx, int64_t nx, const int32_t* ix, const float* Y, int64_t ldy, int64_t ny,
                                const int32_t* iy, int64_t n_pairs, int H, int W, int planes, const float* w1, int win, float c1, float c2, float* ssim,

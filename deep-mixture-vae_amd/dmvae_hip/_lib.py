@@ -53,6 +53,7 @@ EXPORTS = [
     "dmvae_prdc_counts",
     "dmvae_sinkhorn_softmin",
     "dmvae_binarize_rows",
+    "dmvae_augment_rows",
     "dmvae_ssim_rows",
     "dmvae_softmax_xent_ws_bytes", "dmvae_softmax_xent", "dmvae_linear_scores",
     "dmvae_graph_sym_normalize", "dmvae_label_spread_ws_bytes", "dmvae_label_spread",
@@ -104,6 +105,11 @@ class GmmSeedConfig(C.Structure):
     """dmvae_gmm_seed_config"""
     _fields_ = [("N", C.c_int32), ("D", C.c_int32), ("K", C.c_int32), ("n_init", C.c_int32), ("local_trials", C.c_int32),
                 ("seed", C.c_uint64), ("flags", C.c_int32)]
+
+
+class AugmentParams(C.Structure):
+    """dmvae_augment_params: the ranges of the random affine draw"""
+    _fields_ = [("rotate_deg", C.c_float), ("translate_px", C.c_float), ("scale_lo", C.c_float), ("scale_hi", C.c_float), ("shear_deg", C.c_float)]
 
 
 class Epilogue(C.Structure):
@@ -320,6 +326,7 @@ def _load():
         "dmvae_prdc_counts": [vp, vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp],
         "dmvae_sinkhorn_softmin": [vp, vp, i64, i32, vp, i64, i32, i32, vp, vp, f32, vp, vp],
         "dmvae_binarize_rows": [vp, vp, i64, i64, i32, i64, u64, u64, i32, vp, i64],
+        "dmvae_augment_rows": [vp, vp, i64, i64, i32, i32, i64, u64, u64, P(AugmentParams), vp, vp, vp, i64],
         "dmvae_ssim_rows": [vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, i32, i32, i32, vp, i32, f32, f32, vp, vp, vp],
         "dmvae_softmax_xent_ws_bytes": [i64, i32, i32],
         "dmvae_softmax_xent": [vp, vp, i64, i64, i32, vp, vp, vp, i32, vp, i64, vp, vp, i64, vp, vp],

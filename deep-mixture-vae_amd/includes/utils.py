@@ -182,9 +182,14 @@ class Dataset:
     binarize ("off" = the reference, grey levels as soft targets): "static" one Bernoulli draw of the rows, "dynamic" a
     fresh draw per epoch -- the draw counter is the number of reshuffle() calls so far --, "threshold" x > 0.5.  The draw is made on the
     device (dmvae_hip.binarize) into a second resident buffer that device_rows returns in place of the grey rows; binarize_seed keys it, and
-    the ranks of a data-parallel run pass the same one: they hold the whole data set and must agree on it.  No NumPy draw is consumed."""
+    the ranks of a data-parallel run pass the same one: they hold the whole data set and must agree on it.  No NumPy draw is consumed.
 
-    def __init__(self, data, batch_size=100, shuffle=True, binarize="off", binarize_seed=0, labeled=None):
+    augment (None = off): a dmvae_hip.augment.AugmentSpec or its string.  train_rows(device) then returns a further
+    resident buffer with every grey row warped by its own random affine map, redrawn per epoch like the "dynamic" draw (counter = reshuffle()
+    calls so far, keyed by augment_seed, the same on every rank) and, with binarize != "off", binarised after the warp.  device_rows, data,
+    get_batches and the labels stay the clean rows."""
+
+    def __init__(self, data, batch_size=100, shuffle=True, binarize="off", binarize_seed=0, labeled=None, augment=None, augment_seed=0):
         data, classes = data
         if binarize not in BINARIZE_MODES:
             raise ValueError("binarize = %r: one of %s" % (binarize, ", ".join(BINARIZE_MODES)))
@@ -205,6 +210,13 @@ class Dataset:
         self._reshuffles = 0                   # reshuffle() calls so far: the draw counter of "dynamic"
         self._draws = {}                       # device -> the counter of the draw its binarised buffer holds
         self._host_draw = None                 # (counter, rows): the current draw, read back once
+        self.augment = None
+        self.augment_seed = int(augment_seed)
+        self._train_draws = {}                 # device -> (augment counter, binarise counter) of the draw its training buffer holds
+        if augment is not None:
+            from dmvae_hip.augment import parse_augment
+            self.augment = parse_augment(augment)
+            self.augment.shape_for(self.data_dim)              # (refuses rows that are no H x W image before anything is uploaded)
         if shuffle:
             self.order = self.order[np.random.permutation(len(self._rows))]
 
@@ -239,6 +251,44 @@ class Dataset:
         if self.binarize == "off":
             return self._device[key]
         return self._binarized_rows(device)
+
+    def train_rows(self, device):
+        """the rows an epoch trains on: device_rows(device) itself without augmentation; with it, a resident buffer of its own whose address
+        never changes, holding the warp of the GREY rows under counter draw_counter_augment() -- then binarised, in the data set's mode, seed
+        and counter, when binarize != "off" -- redrawn in place on the current stream when stale"""
+        if self.augment is None:
+            return self.device_rows(device)
+        return self._augmented_rows(device)
+
+    def draw_counter_augment(self):
+        """the Philox counter of the current augmentation draw: reshuffle() calls so far"""
+        return self._reshuffles
+
+    def _augmented_rows(self, device):
+        import torch
+        from dmvae_hip.augment import augment
+        key = str(device)
+        if key not in self._device:
+            self._device[key] = torch.as_tensor(self._rows).to(device)
+        grey = self._device[key]
+        if "augmented:" + key not in self._device:
+            self._device["augmented:" + key] = torch.empty_like(grey)
+            if self.binarize != "off":
+                self._device["train:" + key] = torch.empty_like(grey)
+        warped = self._device["augmented:" + key]
+        want = (self.draw_counter_augment(), self.draw_counter())
+        if self.binarize == "off":
+            if self._train_draws.get(key) != want:
+                augment(grey, self.augment, seed=self.augment_seed, counter=want[0], out=warped)
+                self._train_draws[key] = want
+            return warped
+        from dmvae_hip.binarize import binarize
+        out = self._device["train:" + key]
+        if self._train_draws.get(key) != want:
+            augment(grey, self.augment, seed=self.augment_seed, counter=want[0], out=warped)
+            binarize(warped, seed=self.binarize_seed, counter=want[1], mode="threshold" if self.binarize == "threshold" else "bernoulli", out=out)
+            self._train_draws[key] = want
+        return out
 
     def draw_counter(self):
         """the Philox counter of the current draw: reshuffle() calls so far under "dynamic", 0 otherwise"""

@@ -183,6 +183,10 @@ class MoE:
             return 1 - error / data.len, acc_cl
         return -error / data.epoch_len, acc_cl
 
+    def get_augmentation_consistency(self, session, data, augment, n_draws=4, seed=0, counter=0):
+        raise NotImplementedError("get_augmentation_consistency with %s: the MoE data set carries regression labels that are functions of the "
+                                  "grey rows, and a warped row has none; the evaluator is built for DeepMixtureVAE and VaDE" % type(self).__name__)
+
     def get_cluster_metrics(self, session, data, silhouette=True, counter=0, return_labels=False):
         """The gate's cluster quality (DeepMixtureVAE.get_cluster_metrics): dict(acc, nmi, ari, purity, silhouette, n_clusters_used)
         of the experts' arg-max against the classes, the matrix sized max(E, n_classes) as get_accuracy sizes it.  No reshuffle."""

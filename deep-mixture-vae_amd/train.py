@@ -38,6 +38,10 @@ the exact t-SNE in HIP, dmvae_hip.tsne.TSNE),
 draw of every row; dynamic: a fresh draw of the train set per epoch, the test set and the --knn / --probe split static; threshold: x > 0.5 --
 so that llTest is a Bernoulli log-likelihood in nats, comparable with the literature's binarised-MNIST figures; off = the reference's grey
 levels as soft targets) and --binarize_seed (the key of the draws, the same on every rank),
+--augment SPEC / --augment_seed S (dmvae / vade: every epoch trains on a fresh random affine warp of every train row, drawn and applied on the
+device -- SPEC e.g. rotate=10,translate=2,scale=0.9:1.1,shear=5 in degrees, pixels and factors; the test set and every evaluation stay clean;
+off by default) and --aug_consistency SPEC / --aug_draws J (per epoch on the test set: augAgree, the share of rows that keep their cluster
+under J random warps of SPEC, and the accuracy of the warped rows under the clean matching, get_augmentation_consistency),
 --n_labeled L / --label_weight A / --label_seed S (dmvae, one rank: semi-supervised training -- L rows of the train split, stratified by
 class, keep their label and every step adds A * N / L * the cross-entropy of q(c|x) = softmax(logits) on the labelled rows of its batch
 (csrc/label_xent.hip), which pulls cluster c onto class c; the epoch line gains accDirect, the share of test rows whose arg-max cluster IS
@@ -179,6 +183,16 @@ parser.add_argument("--n_labeled", type=int, default=0,
 parser.add_argument("--label_weight", type=float, default=1.0,
                     help="--n_labeled: alpha, the weight of the mean cross-entropy of the labelled set against the per-row VAE loss")
 parser.add_argument("--label_seed", type=int, default=0, help="--n_labeled: the seed of the stratified draw (its own RandomState)")
+parser.add_argument("--augment", type=str, default=None, metavar="SPEC",
+                    help="dmvae / vade: train every epoch on a fresh random affine warp of the train rows (Dataset(augment=...), csrc/augment.hip): "
+                         "SPEC is rotate=DEG,translate=PX,scale=LO:HI,shear=DEG with any key left out; the rows are square images.  The test set, "
+                         "the --knn / --probe split and every evaluator keep the clean rows.  Default: off.")
+parser.add_argument("--augment_seed", type=int, default=0,
+                    help="--augment: the seed of the draws (Philox stream 9); every rank of a data-parallel run uses this same value")
+parser.add_argument("--aug_consistency", type=str, default=None, metavar="SPEC",
+                    help="dmvae / vade: per epoch, the share of test rows whose cluster survives a random warp of SPEC (augAgree) and the accuracy "
+                         "of the warped rows under the clean rows' matching (get_augmentation_consistency)")
+parser.add_argument("--aug_draws", type=int, default=4, help="--aug_consistency: warps per row")
 parser.add_argument("--binarize_seed", type=int, default=0,
                     help="--binarize: the seed of the draws (Philox stream 8); every rank of a data-parallel run uses this same value, not a "
                          "per-rank one: the ranks hold the whole data set and must agree on it")
@@ -320,7 +334,7 @@ def main(argv):
         from includes.utils import choose_labeled
         labeled = choose_labeled(train_classes, argv.n_labeled, n_clusters, argv.label_seed, rows=np.arange(len(dataset.train_data)))
     train_data = Dataset((train_data, train_classes), batch_size=argv.batch_size, binarize=argv.binarize, binarize_seed=argv.binarize_seed,
-                         labeled=labeled)
+                         labeled=labeled, augment=argv.augment, augment_seed=argv.augment_seed)
 
     # --knn votes among the train split alone (train_data holds the test rows too: each would find itself) and --probe fits on it;
     # unshuffled, so that nothing is drawn from the NumPy stream and the run trains as it does without the flags
@@ -390,6 +404,8 @@ def main(argv):
             probeTest = model.get_linear_probe_accuracy(sess, probe_data, test_data, C=argv.probe_C) if probe_data is not None else None
             flTest = (model.get_few_label_accuracy(sess, few_data, test_data, n_labeled=argv.few_label, seed=argv.few_label_seed)
                       if few_data is not None else None)
+            acTest = (model.get_augmentation_consistency(sess, test_data, argv.aug_consistency, n_draws=argv.aug_draws, counter=epoch)
+                      if argv.aug_consistency and rank == 0 else None)
             sqTest = model.get_sample_quality(sess, test_data, k=argv.sample_quality, counter=epoch) if argv.sample_quality > 0 and rank == 0 else None
             skTest = model.get_sample_distance(sess, test_data, counter=epoch) if argv.sample_distance and rank == 0 else None
             rqTest = model.get_reconstruction_quality(sess, test_data) if argv.recon_quality and rank == 0 else None
@@ -420,7 +436,7 @@ def main(argv):
                 rec = dict(epoch=epoch, **ep, images_per_sec=(ep.get("rows", 0) / sec if sec else None), train_seconds=sec,
                            acc_train=float(accTrain), acc_test=float(accTest), max_acc=float(max(maxAcc, accTest) if improved else maxAcc),
                            eval_seconds=eval_seconds, eval=argv.eval, world=world, batch_size=argv.batch_size, dtype=argv.dtype, model=model_str,
-                           binarize=argv.binarize)
+                           binarize=argv.binarize, augment=str(train_data.augment) if train_data.augment is not None else "off")
                 if accDirect is not None:      # (label_xent / label_rows / label_acc are in last_epoch)
                     rec.update(acc_direct_test=float(accDirect), n_labeled=argv.n_labeled, label_weight=argv.label_weight)
                 if llTest is not None:
@@ -435,6 +451,9 @@ def main(argv):
                     rec.update(probeTest=float(probeTest), probe_C=argv.probe_C, probe_iters=model.last_linear_probe_.n_iter_)
                 if flTest is not None:
                     rec.update(_few_label_record(flTest))
+                if acTest is not None:
+                    rec.update(aug_agree=float(acTest["agree"]), aug_acc=float(acTest["acc_aug"]), aug_acc_clean=float(acTest["acc_clean"]),
+                               aug_agree_per_class=[None if math.isnan(x) else float(x) for x in acTest["agree_per_class"]])
                 if sqTest is not None:
                     rec.update(_sample_quality_record(sqTest))
                 if skTest is not None:
@@ -463,6 +482,8 @@ def main(argv):
                 postfix["probeTest"] = "%.4f" % probeTest
             if flTest is not None:
                 postfix["flTest"] = "%.4f" % flTest["accuracy"]
+            if acTest is not None:
+                postfix["augAgree"] = "%.4f" % acTest["agree"]
             if sqTest is not None:
                 postfix.update(precTest="%.4f" % sqTest["precision"], covTest="%.4f" % sqTest["coverage"])
             if skTest is not None:
@@ -492,6 +513,9 @@ def main_moe(argv, world, rank):
     import models
     from dmvae_hip import Session
     from includes.utils import MEDataset
+    if argv.augment or argv.aug_consistency:
+        raise ValueError("--augment / --aug_consistency with --model %s: the regression labels are functions of the grey rows; the MoE data set is not "
+                         "augmented" % argv.model)
     if argv.binarize != "off":
         raise ValueError("--binarize %s with --model %s: the regression labels are functions of the grey rows; the MoE data set is not binarised"
                          % (argv.binarize, argv.model))

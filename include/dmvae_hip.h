@@ -892,6 +892,37 @@ int dmvae_sinkhorn_softmin(void* stream, const float* X, int64_t ldx, int N, con
 int dmvae_binarize_rows(void* stream, const float* X, int64_t ldx, int64_t n_rows, int n_cols, int64_t row_base, uint64_t seed, uint64_t counter,
                         int mode, float* out, int64_t ldo);
 
+/* ---- random affine augmentation of rows on the device (csrc/augment.hip).  The reference has none of it.  A row of
+ * X [n_rows][ldx] (f32, unit column stride) is ONE single-plane image of H x W pixels, row-major (n_cols = H W; 1 <= H, W <= 64); out
+ * [n_rows][ldo] gets its warp.  theta (six floats m00 m01 m02 m10 m11 m12 per row) is the SAMPLING map in pixel-index units, from output
+ * pixel (row i, column j) to the source coordinate
+ *   sx = m00 j + m01 i + m02,   sy = m10 j + m11 i + m12      (float32: fmaf(m00, j, fmaf(m01, i, m02)), and alike for sy),
+ * and the output value is the bilinear interpolation of the source image extended by zeros -- each of the four taps outside [0, W) x [0, H)
+ * contributes 0: torch's grid_sample(mode = "bilinear", padding_mode = "zeros", align_corners = True) after the unit conversion.  With
+ * x0 = floor(sx), fx = sx - x0 (and y alike):  top = fmaf(fx, v01 - v00, v00), bot = fmaf(fx, v11 - v10, v10), out = fmaf(fy, bot - top, top).
+ * A NaN or Inf coordinate gives 0.  Integer maps copy bits.
+ * theta_in [n_rows][6] (device) gives the maps; with theta_in NULL they are DRAWN from p: uniforms of Philox stream 9 at (seed, step = counter),
+ * blocks 2 g and 2 g + 1 with g = row_base + r, the row's index in the unpermuted data set -- so chunked calls with their own row_base equal
+ * one call in bits, and batch size, row order and rank count do not enter.  u = (w >> 8) 2^-24, s = 2 u - 1.  Block 2 g, words 0 .. 3:
+ * angle = rotate_deg s0, tx = translate_px s1, ty = translate_px s2, scale = exp(log lo + u3 (log hi - log lo)); block 2 g + 1, word 0:
+ * shear = shear_deg s0 (words 1 .. 3 are reserved).  The forward transform acts about the centre c = ((W - 1) / 2, (H - 1) / 2),
+ *   p_out = c + t + R(angle) Shear_x(tan shear) scale (p_in - c),
+ * and theta is its inverse, formed in closed form on the device (csrc/augment.hip states the float32 order).  All-zero ranges with
+ * scale (1, 1) give the identity and out == X in bits.  theta_out [n_rows][6] (device, or NULL) receives the maps used.  Pad columns of out
+ * (H W <= c < ldo) are never written.  The call only enqueues and never synchronises; every argument is checked before anything is enqueued
+ * (DMVAE_EINVAL with the entry's name in the error text: a null X / out; p and theta_in both null; n_rows < 1; H or W outside 1 .. 64;
+ * ldx < H W; ldo < H W; row_base < 0; 2 (row_base + n_rows) >= 2^56; out overlapping X; and, when the maps are drawn, a range that is not
+ * finite or is negative, scale_lo <= 0 or scale_lo > scale_hi). */
+typedef struct dmvae_augment_params {
+    float rotate_deg;     /* angle uniform in [-rotate_deg, rotate_deg) degrees */
+    float translate_px;   /* tx, ty uniform in [-translate_px, translate_px) pixels */
+    float scale_lo;       /* scale log-uniform in [scale_lo, scale_hi] */
+    float scale_hi;
+    float shear_deg;      /* shear angle uniform in [-shear_deg, shear_deg) degrees */
+} dmvae_augment_params;
+int dmvae_augment_rows(void* stream, const float* X, int64_t ldx, int64_t n_rows, int H, int W, int64_t row_base, uint64_t seed, uint64_t counter,
+                       const dmvae_augment_params* p, const float* theta_in, float* theta_out, float* out, int64_t ldo);
+
 /* ---- structural similarity on the device (csrc/ssim.hip): the SSIM of Wang et al. 2004 and the squared error of
  * n_pairs comparisons of image rows.  The reference has none of it.  Comparison r reads row X[ix ? ix[r] : r] and row Y[iy ? iy[r] : r]
  * (ix, iy: device int32 [n_pairs] or NULL; X and Y may be the same buffer).  A row is `planes` images of H x W f32, one after another; ldx,
